@@ -10,10 +10,17 @@ starts and outputs stay device-resident (the device analog of the reference's
 memory partitions; PCIe-inclusive rates are reported in DESIGN.md §Measurement).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
-         [--mb-per-gpu MB] [--base-rows R] [--dirty F] [--cpu-seconds S]
-         [--pmc-summary FILE]
+         [--mb-per-gpu MB] [--base-rows R] [--dirty F]
+         [--dump-outputs DIR] [--full [--cpu-seconds S] [--e2e-mb MB]]
+         [--pmc-db DIR ...]
 Launched for N>1 by torchrun (one rank per GPU; RANK/LOCAL_RANK/WORLD_SIZE env).
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, print the line. --full adds the legs that take runs of their own (the
+end-to-end file->file leg and the host-core cpu_baseline); their keys are
+absent/null in a plain line. --dump-outputs DIR writes what the timed path
+computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -170,6 +177,67 @@ def e2e_leg(header, body, mb, local_rank=0, dist=None, rank=0, world=1):
             shutil.rmtree(tdir, ignore_errors=True)
 
 
+DUMP_SAMPLE_BYTES = 12 << 20   # csv text bytes sampled (x4 as float32 = 48 MB)
+DUMP_BLOCK = 4096
+DUMP_SEGMENT = 1 << 20
+
+
+def dump_outputs(dirpath, glib, stage, dev, nbytes, last):
+    """Write what the timed path computed in its last step as DIR/<name>.npy.
+
+    The timed path leaves its output partition on the device and hands the
+    caller counts only, so:
+      counts.npy            float64 [in_rows, out_rows, bytes_in, bytes_out,
+                            exception_rows] of the last timed step
+    and the csv text itself comes from one more, untimed execution of the same
+    stage over the same resident input with the device->host copy enabled
+    (its counts must equal the last timed step's, else this raises):
+      out_csv_segment_sums.npy  float64 byte sum of every 1 MiB segment of the
+                                whole output text (covers every byte)
+      out_csv_sample.npy        float32 output text bytes — all of them up to
+                                12 MiB, else a fixed seeded sample of 4 KiB
+                                blocks (block choice depends only on the
+                                output length)
+    Inputs are seeded, so two builds run with the same arguments can be
+    compared file by file."""
+    import numpy as np
+    from tuplex_amd.engine import TpxResult
+    os.makedirs(dirpath, exist_ok=True)
+    keys = ("in_rows", "out_rows", "bytes_in", "bytes_out", "exc")
+    np.save(os.path.join(dirpath, "counts.npy"),
+            np.array([last[k] for k in keys], dtype=np.float64))
+    res = TpxResult()
+    rc = glib.lib.tpx_stage_execute_csv_dev(stage, dev, nbytes, 0, 0,
+                                            ctypes.byref(res))
+    if rc != 0:
+        raise RuntimeError(glib.err())
+    try:
+        again = {"in_rows": res.in_num_rows, "out_rows": res.out_num_rows,
+                 "bytes_in": res.bytes_in, "bytes_out": res.bytes_out,
+                 "exc": res.exc_num_rows}
+        if any(again[k] != last[k] for k in keys):
+            raise RuntimeError("read-back execution disagrees with the last "
+                               "timed step: %r vs %r" % (again, last))
+        text = np.frombuffer(ctypes.string_at(res.out_data, res.out_size),
+                             dtype=np.uint8)
+    finally:
+        glib.lib.tpx_result_free(ctypes.byref(res))
+    nfull = len(text) // DUMP_SEGMENT
+    sums = text[:nfull * DUMP_SEGMENT].reshape(nfull, DUMP_SEGMENT).sum(
+        axis=1, dtype=np.float64)
+    if len(text) > nfull * DUMP_SEGMENT:
+        sums = np.append(sums, text[nfull * DUMP_SEGMENT:].sum(
+            dtype=np.float64))
+    np.save(os.path.join(dirpath, "out_csv_segment_sums.npy"), sums)
+    if len(text) > DUMP_SAMPLE_BYTES:
+        nblocks = len(text) // DUMP_BLOCK
+        pick = np.sort(np.random.default_rng(0).choice(
+            nblocks, size=DUMP_SAMPLE_BYTES // DUMP_BLOCK, replace=False))
+        text = text[:nblocks * DUMP_BLOCK].reshape(nblocks, DUMP_BLOCK)[pick]
+    np.save(os.path.join(dirpath, "out_csv_sample.npy"),
+            text.astype(np.float32).ravel())
+
+
 def parse_pmc_dbs(paths):
     """HBM traffic per tpx_stage_main launch from rocprofv3 rocpd sqlite dbs
     (separate FETCH_SIZE and WRITE_SIZE passes — they don't fit one TCC pass).
@@ -221,11 +289,22 @@ def main():
     ap.add_argument("--pmc-db", type=str, nargs="*", default=None,
                     help="rocprofv3 output dirs (FETCH_SIZE / WRITE_SIZE passes "
                          "at THIS workload config) for roofline.traffic")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the "
+                         "end-to-end file->file leg (config.e2e_*) and the "
+                         "host-core cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the end-to-end leg")
     ap.add_argument("--e2e-mb", type=int, default=None,
                     help="end-to-end file->file leg size (default: mb-per-gpu)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path "
+                         "computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -317,10 +396,14 @@ def main():
         total_rows = float(sum(k["in_rows"] for k in kstats))
         total_bytes = float(sum(k["bytes_in"] + k["bytes_out"] for k in kstats))
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, glib, stage, dev, len(body),
+                     kstats[-1])
+
     # e2e leg is collective at world>1 (engine-path sharding) — every rank
     # must enter it before non-zero ranks exit
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         e2e = e2e_leg(header, body, args.e2e_mb or args.mb_per_gpu,
                       local_rank % ndev, dist=dist, rank=rank, world=world)
     if rank != 0:
@@ -349,7 +432,7 @@ def main():
                         "write": last["t_write_ms"]},
     }
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world <= 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world <= 1:
         cpu = cpu_baseline_leg(body, args.cpu_seconds)
     line = {
         "metric": "rows/s",

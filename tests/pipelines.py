@@ -331,8 +331,13 @@ def compile_collected(jobs, workers=None, verbose=False):
     import multiprocessing as _mp
     nw = workers or min(8, _os.cpu_count() or 8)
     ctx = _mp.get_context("spawn")
+    # longest sources first, and a progress line per ten stages
+    jobs = sorted(jobs, key=lambda j: -len(j[0]))
     with ProcessPoolExecutor(max_workers=nw, mp_context=ctx) as ex:
-        list(ex.map(_compile_one_job, jobs))
+        for i, _ in enumerate(ex.map(_compile_one_job, jobs), 1):
+            if i % 10 == 0 or i == len(jobs):
+                print("compiled %d/%d stage kernels" % (i, len(jobs)),
+                      flush=True)
     return len(jobs)
 
 
@@ -487,7 +492,7 @@ def precompile_tests(verbose=False):
             src, desc = codegen.generate_stage(sp, source="mem", sink="mem")
             _stage_compile(glib, src, desc)
             n += 1
-    # flights + 2 joins (the 110-col stage: ~13 min of cold hipRTC)
+    # flights + 2 joins (the 110-col stage)
     from tests import extra_data as X
     from tests.test_join import FL_J1, FL_J2, _post_join_map, _post_join_keep
     from tuplex_amd import csvio

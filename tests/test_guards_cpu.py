@@ -28,7 +28,7 @@ def test_compilable_pipeline_fails_loudly_without_gpu():
         ds.collect()
 
 
-def test_czillow_matches_oracle_row_counts():
+def test_czillow_matches_oracle_row_counts(tmp_path):
     """The cpu_baseline C port must produce exactly the oracle's output rows on
     the same input (it is a restatement, not just a timer)."""
     from oracle import pyoracle_csv
@@ -39,7 +39,7 @@ def test_czillow_matches_oracle_row_counts():
     if not os.path.exists(binp):
         subprocess.check_call(["make", "-C", os.path.join(REPO, "oracle"), "-s"])
     data, _ = make_zillow_csv_bytes(5000, seed=99, dirty_frac=0.02)
-    tmp = "/tmp/tpx_czillow_test.csv"
+    tmp = str(tmp_path / "tpx_czillow_test.csv")
     with open(tmp, "wb") as f:
         f.write(data)
     out = json.loads(subprocess.check_output([binp, tmp, "0"]))

@@ -2745,5 +2745,23 @@ def generate_stage(sp, source="mem", sink="mem", csv_info=None):
     cg1.generate()
     groups = {k: v for k, v in cg1.scan_registry.items() if len(v) >= 2}
     # pass 2: fresh instance (lits/emitter state are single-use)
-    return StageCodegen(sp, source, sink, csv_info,
-                        fusion_groups=groups or None).generate()
+    src, desc = StageCodegen(sp, source, sink, csv_info,
+                             fusion_groups=groups or None).generate()
+    return _outline_wide_cell_walk(src), desc
+
+
+# A wide CSV stage (the 110-column flights shape) walks one cell per column in
+# each of its two row bodies; with the mask walk force-inlined at all ~220 call
+# sites tpx_stage_main grows so large that hipRTC needs 13-20 minutes for it
+# (seconds with the walk outlined). Narrow stages keep the inlined walk and
+# their source text byte for byte.
+_WIDE_CELL_WALK_CALLS = 64
+_MW_CELL_INLINE = "__device__ __forceinline__ void tpx_mw_cell("
+_MW_CELL_OUTLINE = "__device__ __attribute__((noinline)) void tpx_mw_cell("
+
+
+def _outline_wide_cell_walk(src):
+    if src.count("tpx_mw_cell(S,") <= _WIDE_CELL_WALK_CALLS:
+        return src
+    assert src.count(_MW_CELL_INLINE) == 1
+    return src.replace(_MW_CELL_INLINE, _MW_CELL_OUTLINE)
