@@ -40,6 +40,18 @@ def runtime_header() -> str:
     return _RT_HEADER_CACHE
 
 
+_RE_HEADER_CACHE = None
+
+
+def regex_header() -> str:
+    global _RE_HEADER_CACHE
+    if _RE_HEADER_CACHE is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                            "csrc", "tpx_re.hip.h")
+        _RE_HEADER_CACHE = open(path).read()
+    return _RE_HEADER_CACHE
+
+
 def _ctype(t):
     base = T.deopt(t)
     if base in (T.I64,):
@@ -167,6 +179,20 @@ class StageCodegen:
             self.lit_defs.append(
                 '__device__ const char %s[%d] = "%s";' % (name, len(b) + 1, _esc(s)))
         return "tstr{%s, %d}" % (self.lits[s], len(s.encode("utf-8")))
+
+    def re_prog(self, prog) -> str:
+        """Embed a lowered regex program (udf/relower.py) once per stage, like
+        a string literal; returns the array name."""
+        if not hasattr(self, "re_progs"):
+            self.re_progs = {}
+            self.re_defs = []
+        key = tuple(prog.words)
+        if key not in self.re_progs:
+            name = "re_prog%d" % len(self.re_progs)
+            self.re_progs[key] = name
+            self.re_defs.append("__device__ const int %s[%d] = {%s};"
+                                % (name, len(key), ",".join(map(str, key))))
+        return self.re_progs[key]
 
     @staticmethod
     def _struct_key(node):
@@ -796,6 +822,33 @@ class StageCodegen:
             em.w("tstr %s = tpx_splitget(%s, %s, %s, &_ec);" % (r, x, y, z))
             self._check(em, opid)
             return (r, None)
+        if op == "re_exec":
+            # one VM run per call site per row; every group of the match reads
+            # this captures array (value = array name, "null" = no match)
+            x, _ = ev(a[0])
+            prog = self.re_prog(n["prog"])
+            cp = em.fresh("cp")
+            em.w("int %s[%d];" % (cp, 2 * (n["prog"].ngroups + 1)))
+            em.w("bool %s_n = !tpx_re_exec(%s, %s, %s, &_ec);" % (cp, prog, x, cp))
+            self._check(em, opid)
+            return (cp, cp + "_n")
+        if op == "re_matched":
+            _cp, nomatch = ev(a[0])
+            r = em.fresh("b")
+            em.w("bool %s = !%s;" % (r, nomatch))
+            return (r, None)
+        if op == "re_group":
+            cp, nomatch = ev(a[0])
+            x, _ = ev(a[0]["args"][0])
+            # None[k] -> TypeError, None.group(k) -> AttributeError
+            em.w("if (%s) return ((long long)%d) | ((long long)%d << 32);"
+                 % (nomatch, 129 if n["v"] == "item" else 106, opid))
+            r = em.fresh("s")
+            em.w("tstr %s = tpx_re_group(%s, %s, %d);" % (r, x, cp, n["w"]))
+            if T.is_opt(n["t"]):
+                em.w("bool %s_n = %s[%d] < 0;" % (r, cp, 2 * n["w"]))
+                return (r, r + "_n")
+            return (r, None)
         if op == "fmt_int":
             x, _ = ev(a[0])
             r = em.fresh("s")
@@ -1168,6 +1221,10 @@ class StageCodegen:
         if op in ("slice", "getitem", "strip", "lower", "upper", "swapcase",
                   "splitget"):
             return self._qfree_node(a[0], env)
+        if op == "re_group":  # a view into the match's subject string
+            return self._qfree_node(a[0]["args"][0], env)
+        if op == "re_matched":
+            return True
         if op == "concat":
             return self._qfree_and(self._qfree_node(a[0], env),
                                    self._qfree_node(a[1], env))
@@ -1343,7 +1400,7 @@ class StageCodegen:
             "// generated by tuplex_amd.codegen — stage %s" % sp.signature(),
             runtime_header(),
             "",
-        ] + self.lit_defs + self.join_defs + [
+        ] + self._re_section() + self.lit_defs + self.join_defs + [
             "",
             "struct Out {",
         ] + out_fields + [
@@ -1360,6 +1417,14 @@ class StageCodegen:
         ]
         desc = self._desc(in_types, store_types)
         return "\n".join(src), desc
+
+    def _re_section(self):
+        """Regex VM header + embedded programs — only for stages that run a
+        regex, so every other stage's source (the hsaco cache key) is
+        unchanged."""
+        if not getattr(self, "re_defs", None):
+            return []
+        return [regex_header(), ""] + self.re_defs
 
     def _process_signature(self, in_types):
         params = []

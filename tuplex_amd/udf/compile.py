@@ -13,13 +13,27 @@ Supported expressions: constants, names, bin/bool/unary ops, chained comparisons
 `in`, IfExp, str method calls (find/rfind/lower/upper/replace/strip/startswith/
 endswith/swapcase), len/int/float/str/abs, subscript (column access, str index,
 str slice), '%0Nd' % x format, tuple literals (return position only).
+
+Regular expressions: re.search(P, s) / re.match(P, s) / re.fullmatch(P, s) with
+exactly two arguments, where `re` is the real module (global or closure) and P
+folds to a compile-time str (literal, global/closure constant, a local bound
+to one, `+` concatenations). The match value m may be used as a truth value
+(`if m`, `m if .. else ..`, `not m`, and/or inside a condition), compared with
+None (`is`, `is not`), and read with m[k] / m.group(k) / m.group() for a
+constant 0 <= k <= ngroups. It cannot be returned, stored in a tuple or passed
+anywhere else. Pattern subset: udf/relower.py (CPython's own parser; anything
+not lowered on purpose — back-references, look-around, flags, ... — is a
+UDFCompileError). m[k] on a failed match raises TypeError, m.group(k)
+AttributeError, as in CPython.
 """
 import ast
 import inspect
+import re as _re_module
 import textwrap
 from typing import Callable, Dict, List, Optional
 
 from .. import ttypes as T
+from . import relower
 from . import tir
 
 
@@ -124,11 +138,18 @@ class _Compiler:
             raise UDFCompileError("UDF arity %d vs row arity %d"
                                   % (len(args), len(self.input_types)))
         if isinstance(node, ast.Lambda):
-            return self.expr(node.body, env)
+            return self._no_match(self.expr(node.body, env))
         res = self.exec_stmts(node.body, 0, env)
         if isinstance(res, _Ret):
-            return res.node
+            return self._no_match(res.node)
         raise UDFCompileError("UDF may fall off the end (implicit None return)")
+
+    @staticmethod
+    def _no_match(node):
+        """A match value is internal to the UDF body: it has no column type."""
+        if node["t"] == tir.MATCH:
+            raise UDFCompileError("a match object cannot leave the UDF")
+        return node
 
     # ---- statements ----------------------------------------------------------
     def exec_stmts(self, stmts, i, env):
@@ -154,7 +175,7 @@ class _Compiler:
                 i += 1
                 continue
             if isinstance(s, ast.If):
-                cond = self.expr(s.test, env)
+                cond = self.cond(s.test, env)
                 rest = stmts[i + 1:]
                 r1 = self.exec_stmts(list(s.body) + rest, 0, dict(env))
                 r2 = self.exec_stmts(list(s.orelse) + rest, 0, dict(env))
@@ -171,6 +192,8 @@ class _Compiler:
         return env  # fell off the end
 
     def _merge_ret(self, cond, a, b):
+        if tir.MATCH in (a["t"], b["t"]):
+            raise UDFCompileError("a match object cannot leave the UDF")
         # tuples merge elementwise
         if a.get("op") == "mktuple" and b.get("op") == "mktuple":
             if len(a["args"]) != len(b["args"]):
@@ -188,6 +211,80 @@ class _Compiler:
             return self._expr(e, env)
         except tir.TirError as ex:
             raise UDFCompileError(str(ex))
+
+    def cond(self, e, env):
+        try:
+            return self._cond(e, env)
+        except tir.TirError as ex:
+            raise UDFCompileError(str(ex))
+
+    def _cond(self, e, env):
+        """`e` in a truth-value position (if/elif test, conditional test, `not`
+        operand, and/or operands inside one of those): a match value lowers to
+        an explicit re_matched() BOOL node here, so tir.ifexpr/notop/boolop
+        keep insisting on BOOL."""
+        if isinstance(e, ast.BoolOp):
+            op = "and" if isinstance(e.op, ast.And) else "or"
+            node = self._cond(e.values[0], env)
+            for v in e.values[1:]:
+                node = tir.boolop(op, node, self._cond(v, env))
+            return node
+        if isinstance(e, ast.UnaryOp) and isinstance(e.op, ast.Not):
+            return tir.notop(self._cond(e.operand, env))
+        node = self._expr(e, env)
+        if node["t"] == tir.MATCH:
+            return tir.re_matched(node)
+        return node
+
+    def _const_str(self, e, env):
+        """Fold `e` to a compile-time str (regex patterns), else None."""
+        if isinstance(e, ast.Constant):
+            return e.value if isinstance(e.value, str) else None
+        if isinstance(e, ast.Name):
+            if e.id in env:
+                n = env[e.id]
+                if n["op"] == "const" and isinstance(n.get("v"), str):
+                    return n["v"]
+                return None
+            v = self.globals.get(e.id)
+            return v if isinstance(v, str) else None
+        if isinstance(e, ast.BinOp) and isinstance(e.op, ast.Add):
+            a = self._const_str(e.left, env)
+            b = self._const_str(e.right, env)
+            if a is not None and b is not None:
+                return a + b
+        return None
+
+    def _is_re_module(self, e, env):
+        return (isinstance(e, ast.Name) and e.id not in env
+                and self.globals.get(e.id) is _re_module)
+
+    def _re_call(self, e, env):
+        mode = e.func.attr
+        if mode not in ("search", "match", "fullmatch"):
+            raise UDFCompileError("unsupported function re.%s" % mode)
+        if len(e.args) != 2 or e.keywords:
+            raise UDFCompileError(
+                "re.%s takes exactly (pattern, string); flags are not "
+                "supported" % mode)
+        pattern = self._const_str(e.args[0], env)
+        if pattern is None:
+            raise UDFCompileError("re.%s pattern is not a compile-time "
+                                  "string constant" % mode)
+        try:
+            prog = relower.lower(pattern, mode)
+        except relower.ReLowerError as ex:
+            raise UDFCompileError("regex %r: %s" % (pattern, ex))
+        return tir.re_exec(mode, pattern, prog, self._expr(e.args[1], env))
+
+    @staticmethod
+    def _group_index(args):
+        if not args:
+            return 0
+        if len(args) == 1 and args[0]["op"] == "const" and isinstance(
+                args[0].get("v"), int) and not isinstance(args[0]["v"], bool):
+            return args[0]["v"]
+        raise UDFCompileError("match group index must be one constant int")
 
     def _expr(self, e, env):
         if isinstance(e, ast.Constant):
@@ -207,6 +304,8 @@ class _Compiler:
                 return self._fmt(e, env)
             return self._binop_ast(e.op, self._expr(e.left, env), self._expr(e.right, env))
         if isinstance(e, ast.UnaryOp):
+            if isinstance(e.op, ast.Not):
+                return tir.notop(self._cond(e.operand, env))
             v = self._expr(e.operand, env)
             if isinstance(e.op, ast.USub):
                 if v["op"] == "const" and isinstance(v.get("v"), (int, float)):
@@ -231,14 +330,21 @@ class _Compiler:
                 left = right
             return result
         if isinstance(e, ast.IfExp):
-            return tir.ifexpr(self._expr(e.test, env), self._expr(e.body, env),
-                              self._expr(e.orelse, env))
+            test = self._cond(e.test, env)
+            body, orelse = self._expr(e.body, env), self._expr(e.orelse, env)
+            if tir.MATCH in (body["t"], orelse["t"]):
+                raise UDFCompileError("a match object cannot be a "
+                                      "conditional's value")
+            return tir.ifexpr(test, body, orelse)
         if isinstance(e, ast.Call):
             return self._call(e, env)
         if isinstance(e, ast.Subscript):
             return self._subscript(e, env)
         if isinstance(e, ast.Tuple):
             elems = [self._expr(x, env) for x in e.elts]
+            if any(x["t"] == tir.MATCH for x in elems):
+                raise UDFCompileError("a match object cannot be stored in a "
+                                      "tuple")
             return tir.mk("mktuple", T.tup(x["t"] for x in elems), elems)
         raise UDFCompileError("unsupported expression %s" % type(e).__name__)
 
@@ -270,6 +376,15 @@ class _Compiler:
     def _cmp_ast(self, op, a, b):
         m = {ast.Lt: "lt", ast.LtE: "le", ast.Gt: "gt", ast.GtE: "ge",
              ast.Eq: "eq", ast.NotEq: "ne"}
+        if tir.MATCH in (a["t"], b["t"]):
+            # only `m is None` / `m is not None`
+            m, other = (a, b) if a["t"] == tir.MATCH else (b, a)
+            if not isinstance(op, (ast.Is, ast.IsNot)) or not (
+                    other["op"] == "const" and other.get("v") is None):
+                raise UDFCompileError("a match object compares only with "
+                                      "`is None` / `is not None`")
+            matched = tir.re_matched(m)
+            return matched if isinstance(op, ast.IsNot) else tir.notop(matched)
         if isinstance(op, ast.In):
             return tir.call("contains", [b, a])  # contains(haystack, needle)
         if isinstance(op, ast.NotIn):
@@ -285,9 +400,17 @@ class _Compiler:
 
     def _call(self, e, env):
         if isinstance(e.func, ast.Attribute):
+            if self._is_re_module(e.func.value, env):
+                return self._re_call(e, env)
             obj = self._expr(e.func.value, env)
             meth = e.func.attr
             args = [self._expr(a, env) for a in e.args]
+            if obj["t"] == tir.MATCH:
+                if meth != "group" or e.keywords:
+                    raise UDFCompileError("unsupported match method .%s" % meth)
+                return tir.re_group(obj, self._group_index(args), how="group")
+            if any(a["t"] == tir.MATCH for a in args):
+                raise UDFCompileError("a match object cannot be an argument")
             if meth in ("find", "rfind", "lower", "upper", "strip", "replace",
                         "startswith", "endswith", "swapcase", "center"):
                 return tir.call(meth if meth not in ("find", "rfind") else meth,
@@ -296,6 +419,8 @@ class _Compiler:
         if isinstance(e.func, ast.Name):
             name = e.func.id
             args = [self._expr(a, env) for a in e.args]
+            if any(a["t"] == tir.MATCH for a in args):
+                raise UDFCompileError("a match object cannot be an argument")
             if name == "str":
                 return tir.call("to_str", args)
             if name in ("int", "float", "len", "abs"):
@@ -336,6 +461,11 @@ class _Compiler:
             idx = self._expr(e.slice, env)
             return tir.splitget(s, sep, idx)
         obj = self._expr(e.value, env)
+        if obj["t"] == tir.MATCH:
+            if isinstance(e.slice, ast.Slice):
+                raise UDFCompileError("match objects do not slice")
+            return tir.re_group(obj, self._group_index(
+                [self._expr(e.slice, env)]), how="item")
         if isinstance(e.slice, ast.Slice):
             if e.slice.step is not None:
                 raise UDFCompileError("slice step not supported")

@@ -221,6 +221,43 @@ def fmt(spec, arg):
     return mk("fmt_int", T.STR, [arg], w=spec)
 
 
+# Result of re.search/re.match/re.fullmatch with a constant pattern. Internal to
+# a UDF body: never a column type (T.unify knows nothing about it, so an `if`
+# that would merge a match with another value fails to type).
+MATCH = "match"
+
+
+def re_exec(mode, pattern, prog, s):
+    """re.<mode>(pattern, s) lowered to a device VM program (udf/relower.py).
+    mode/pattern live in the `v` field (stage signature, CSE key), the lowered
+    program in `prog`; the only argument is the subject string, so column
+    lineage sees exactly what the UDF reads."""
+    s = _deopt_node(s)
+    if s["t"] != T.STR:
+        raise TirError("re.%s subject must be str" % mode)
+    return mk("re_exec", MATCH, [s], v=(mode, pattern), prog=prog)
+
+
+def re_matched(m):
+    """Truthiness of a match value as an explicit BOOL node."""
+    if m["t"] != MATCH:
+        raise TirError("re_matched needs a match")
+    return mk("re_matched", T.BOOL, [m])
+
+
+def re_group(m, k, how="item"):
+    """m[k] (how='item': TypeError on a failed match) or m.group(k)
+    (how='group': AttributeError). STR, or Option[STR] for a group that need
+    not take part in a match."""
+    if m["t"] != MATCH or m["op"] != "re_exec":
+        raise TirError("group access needs a match")
+    prog = m["prog"]
+    if not (0 <= k <= prog.ngroups):
+        raise TirError("no such group %d (pattern has %d)" % (k, prog.ngroups))
+    t = T.opt(T.STR) if k in prog.optional else T.STR
+    return mk("re_group", t, [m], w=k, v=how)
+
+
 def walk(node, seen=None):
     """Iterate DAG nodes once each (post-order)."""
     if seen is None:
