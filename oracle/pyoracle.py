@@ -91,7 +91,8 @@ def fast_atod(s: str) -> Tuple[bool, float]:
             p += 1
         exponent = 0
         while p < n and "0" <= s[p] <= "9":
-            exponent = exponent * 10 + (ord(s[p]) - 48)
+            # `unsigned int exponent` (StringUtils.cc:114): wraps mod 2^32
+            exponent = (exponent * 10 + (ord(s[p]) - 48)) & 0xFFFFFFFF
             p += 1
         if exponent > 308:
             exponent = 308

@@ -516,6 +516,9 @@ def precompile_tests(verbose=False):
         src, desc = codegen.generate_stage(sp, source="mem", sink="mem")
         _stage_compile(glib, src, desc)
         n += 1
+    # test_gpu_rtops stages (scalar-runtime device slice)
+    from tests import rtops_pipelines
+    n += rtops_pipelines.precompile(glib, _stage_compile)
     return n
 
 

@@ -129,6 +129,21 @@ def test_fast_atod_quirks():
     assert ok and v == float("inf")
 
 
+def test_fast_atod_exponent_wraps_like_unsigned_int():
+    """StringUtils.cc:114-130 accumulates the exponent in an `unsigned int`:
+    it wraps mod 2^32 per digit before the clamp at 308. Expectations recorded
+    from the reference function (double bit patterns)."""
+    import struct
+    recorded = {"1e4294967295": 0x7fe1ccf385ebc8a3,  # clamps to 1e308's product
+                "1e4294967296": 0x3ff0000000000000,  # wraps to e0 -> 1.0
+                "1e4294967297": 0x4024000000000000,  # wraps to e1 -> 10.0
+                "1e-4294967297": 0x3fb999999999999a}
+    for s, bits in recorded.items():
+        ok, v = pyoracle.fast_atod(s)
+        assert ok, s
+        assert struct.unpack("<Q", struct.pack("<d", v))[0] == bits, (s, v)
+
+
 def test_ref_int_matches_python_on_normal():
     for s in ["0", "42", "-7", "  13  ", "1560"]:
         assert pyoracle.ref_int(s) == int(s)

@@ -65,7 +65,7 @@ __device__ __forceinline__ char* tpx_alloc(TpxHeap& h, long long n) {
         if (off + (unsigned long long)n > h.cap) return nullptr;
         return h.base + off;
     }
-    if (h.tl_cur + n > h.tl_end) {
+    if (h.tl_end - h.tl_cur < n) {  // (null - null == 0 before the first chunk)
         unsigned long long off =
             atomicAdd(h.cursor, (unsigned long long)TPX_HEAP_CHUNK);
         if (off + TPX_HEAP_CHUNK > h.cap) return nullptr;
@@ -135,9 +135,13 @@ __device__ __forceinline__ long long tpx_memchr(const char* p, long long n,
     return -1;
 }
 
+// bytes 0..b (inclusive) of a SWAR word
+#define TPX_SWAR_UPTO(b) (~0ULL >> (8 * (7 - (b))))
+
 // tpx_memchr that also ORs the high (non-ASCII) bits of every byte it scans
 // into *hi — lets the CSV cell walk double as the per-row ASCII gate (the walk
-// already touches every row byte; a separate tpx_ascii pass re-reads the row)
+// already touches every row byte; a separate tpx_ascii pass re-reads the row).
+// Exact like the byte loop: bytes after the hit never reach *hi.
 __device__ __forceinline__ long long tpx_memchr_hi(const char* p, long long n,
                                                    char c,
                                                    unsigned long long* hi) {
@@ -159,24 +163,30 @@ __device__ __forceinline__ long long tpx_memchr_hi(const char* p, long long n,
         unsigned long long h3 = tpx_swar_zero(v3 ^ pat);
         if (h0 | h1 | h2 | h3) {
             // hi must cover exactly the bytes scanned up to the hit
-            if (h0) { *hi |= v0 & TPX_SWAR_HIGH;
-                      return i + (__ffsll((long long)h0) - 1) / 8; }
-            *hi |= v0 & TPX_SWAR_HIGH;
-            if (h1) { *hi |= v1 & TPX_SWAR_HIGH;
-                      return i + 8 + (__ffsll((long long)h1) - 1) / 8; }
-            *hi |= v1 & TPX_SWAR_HIGH;
-            if (h2) { *hi |= v2 & TPX_SWAR_HIGH;
-                      return i + 16 + (__ffsll((long long)h2) - 1) / 8; }
-            *hi |= (v2 | v3) & TPX_SWAR_HIGH;
-            return i + 24 + (__ffsll((long long)h3) - 1) / 8;
+            unsigned long long hw, hv;
+            long long base;
+            if (h0) { hw = h0; hv = v0; base = i; }
+            else if (h1) { hw = h1; hv = v1; base = i + 8;
+                           *hi |= v0 & TPX_SWAR_HIGH; }
+            else if (h2) { hw = h2; hv = v2; base = i + 16;
+                           *hi |= (v0 | v1) & TPX_SWAR_HIGH; }
+            else { hw = h3; hv = v3; base = i + 24;
+                   *hi |= (v0 | v1 | v2) & TPX_SWAR_HIGH; }
+            long long b = (__ffsll((long long)hw) - 1) / 8;
+            *hi |= hv & TPX_SWAR_HIGH & TPX_SWAR_UPTO(b);
+            return base + b;
         }
         *hi |= (v0 | v1 | v2 | v3) & TPX_SWAR_HIGH;
     }
     for (; i + 8 <= n; i += 8) {
         unsigned long long v = *(const unsigned long long*)(p + i);
-        *hi |= v & TPX_SWAR_HIGH;
         unsigned long long hit = tpx_swar_zero(v ^ pat);
-        if (hit) return i + (__ffsll((long long)hit) - 1) / 8;
+        if (hit) {
+            long long b = (__ffsll((long long)hit) - 1) / 8;
+            *hi |= v & TPX_SWAR_HIGH & TPX_SWAR_UPTO(b);
+            return i + b;
+        }
+        *hi |= v & TPX_SWAR_HIGH;
     }
     for (; i < n; ++i) {
         *hi |= (unsigned char)p[i] & 0x80u;
@@ -268,8 +278,11 @@ __device__ __forceinline__ bool tpx_ascii(const tstr s) {
     return true;
 }
 
-// vectorized copy: align dest, funnel-shift unaligned source words. May read up
-// to 7 bytes past s+n (every device buffer carries >=16 B tail padding).
+// vectorized copy: align dest, funnel-shift unaligned source words. For n >= 16
+// it reads whole aligned 8-byte words, so it may touch up to 7 bytes BEFORE s
+// and up to 7 bytes past s+n — always within the aligned words that contain
+// s and s+n-1 (every device buffer is 8-aligned with >=16 B padding on both
+// sides). Those extra bytes never reach d (tests/host_rtops_test.cpp).
 __device__ __forceinline__ void tpx_memcpy(char* d, const char* s, long long n) {
     if (n < 16) {
         for (long long i = 0; i < n; ++i) d[i] = s[i];
@@ -322,6 +335,12 @@ __device__ __forceinline__ tstr tpx_to_global(tstr s, const char* lds_lo,
 
 __device__ __forceinline__ long long tpx_floordiv_i64(long long a, long long b, int* ec) {
     if (b == 0) { *ec = EC_ZERODIV; return 0; }
+    if (b == -1) {
+        // LLONG_MIN // -1 == 2^63 is a CPython big int: divert the row to the
+        // interpreter (and never issue the trapping/unspecified division)
+        if (a == -9223372036854775807LL - 1) { *ec = EC_OVERFLOW; return 0; }
+        return -a;
+    }
     long long q = a / b;
     if ((a % b != 0) && ((a < 0) != (b < 0))) q -= 1;  // python floor semantics
     return q;
@@ -329,6 +348,7 @@ __device__ __forceinline__ long long tpx_floordiv_i64(long long a, long long b, 
 
 __device__ __forceinline__ long long tpx_mod_i64(long long a, long long b, int* ec) {
     if (b == 0) { *ec = EC_ZERODIV; return 0; }
+    if (b == -1) return 0;  // x % -1 == 0 in CPython; LLONG_MIN % -1 must not divide
     long long r = a % b;
     if (r != 0 && ((r < 0) != (b < 0))) r += b;
     return r;
@@ -341,13 +361,28 @@ __device__ __forceinline__ double tpx_truediv(double a, double b, int* ec) {
 
 __device__ __forceinline__ double tpx_floordiv_f64(double a, double b, int* ec) {
     if (b == 0.0) { *ec = EC_ZERODIV; return 0.0; }
-    return floor(a / b);
+    // CPython floatobject.c float_floor_div/_float_div_mod restated: the
+    // quotient comes from the exact fmod remainder, not from floor(a / b)
+    // (29.0 // 0.2 is 144.0: a / b rounds up to 145.0). No a*b+c shape here,
+    // so nothing can contract into an FMA.
+    double mod = fmod(a, b);
+    double div = (a - mod) / b;
+    if (mod != 0.0 && ((b < 0.0) != (mod < 0.0))) div -= 1.0;
+    if (div != 0.0) {
+        double fl = floor(div);
+        if (div - fl > 0.5) fl += 1.0;
+        return fl;
+    }
+    return copysign(0.0, a / b);
 }
 
 __device__ __forceinline__ double tpx_mod_f64(double a, double b, int* ec) {
     if (b == 0.0) { *ec = EC_ZERODIV; return 0.0; }
+    // CPython floatobject.c float_rem restated: a zero remainder takes the
+    // sign of the divisor (-4.0 % 2.0 is 0.0, not fmod's -0.0)
     double r = fmod(a, b);
-    if (r != 0.0 && ((r < 0.0) != (b < 0.0))) r += b;
+    if (r != 0.0) { if ((r < 0.0) != (b < 0.0)) r += b; }
+    else r = copysign(0.0, b);
     return r;
 }
 
@@ -481,7 +516,13 @@ __device__ __forceinline__ tstr tpx_center(TpxHeap& h, const tstr s,
 // str * int repetition (python sequence semantics: n <= 0 -> "")
 __device__ __forceinline__ tstr tpx_strmul(TpxHeap& h, const tstr s,
                                            long long n, int* ec) {
-    if (n <= 0 || s.n == 0) return tstr{s.p, 0};
+    if (n <= 0 || s.n <= 0) return tstr{s.p, 0};
+    // CPython raises MemoryError/OverflowError for a repeat that cannot exist;
+    // a product that wraps or exceeds the heap is rejected before any alloc
+    if ((unsigned long long)n > h.cap / (unsigned long long)s.n) {
+        *ec = EC_MEMORYERROR;
+        return tstr{s.p, 0};
+    }
     long long total = s.n * n;
     char* d = tpx_alloc(h, total);
     if (!d) { *ec = EC_MEMORYERROR; return tstr{s.p, 0}; }
@@ -663,16 +704,16 @@ __device__ __forceinline__ tstr tpx_splitget(const tstr s, const tstr sep,
 __device__ __forceinline__ int tpx_fast_atoi64(const char* start, const char* end,
                                                long long* out) {
     if (start == end) return EC_NULLERROR;
-    long long x = 0;
+    unsigned long long x = 0;  // the compiled path's i64 wrap, stated mod 2^64
     const char* p = start;
     bool neg = false;
     if (*p == '-') { neg = true; ++p; }
     while (p < end && *p >= '0' && *p <= '9') {
-        x = x * 10 + (*p - '0');  // i64 wrap like the compiled path
+        x = x * 10 + (unsigned long long)(*p - '0');
         ++p;
     }
     if (p != end) return EC_I64PARSE;
-    *out = neg ? -x : x;
+    *out = (long long)(neg ? 0ULL - x : x);
     return EC_OK;
 }
 
@@ -751,7 +792,8 @@ __device__ __forceinline__ double tpx_float_str(const tstr s, int* ec) {
 
 // int(float): python truncates toward zero; OverflowError outside i64
 __device__ __forceinline__ long long tpx_int_f64(double x, int* ec) {
-    if (!(x > -9.223372036854776e18 && x < 9.223372036854776e18)) {
+    // CPython int(float): -2^63 itself is an i64, +2^63 is not
+    if (!(x >= -9.223372036854775808e18 && x < 9.223372036854775808e18)) {
         *ec = x == x ? EC_OVERFLOW : EC_VALUEERROR;  // NaN -> ValueError
         return 0;
     }
@@ -890,10 +932,11 @@ __device__ __forceinline__ char* tpx_csv_cell_write(char* w, const tstr s) {
 
 // ---- %f output for csv f64 cells (PipelineBuilder.cc:1413 formats doubles
 // with "%f"): EXACT round-half-even of v*10^6 on the binary value via 128-bit
-// fixed point (bit-identical to CPython's correctly-rounded "%f", validated
-// against 500k fuzz doubles). Values whose 6-decimal representation exceeds
-// 63 bits of digits (|v| >~ 9.2e12), nan and inf divert the row (NCV-style:
-// the host formatter produces the identical text on replay). -----------------
+// fixed point (bit-identical to CPython's correctly-rounded "%f"; checked
+// against CPython on 200k+ doubles by tests/test_host_rtops.py). Values whose
+// 6-decimal representation exceeds 63 bits of digits (|v| >~ 9.2e12), nan and
+// inf divert the row (NCV-style: the host formatter produces the identical
+// text on replay). -------------------------------------------------------------
 
 __device__ __forceinline__ int tpx_f64_csv_n(double v, unsigned long long* N,
                                              bool* neg) {
@@ -1154,20 +1197,20 @@ __device__ __forceinline__ long long tpx_memchr_hi_spec(
         unsigned long long h2 = tpx_swar_zero(v2 ^ pat);
         unsigned long long h3 = tpx_swar_zero(v3 ^ pat);
         if (h0 | h1 | h2 | h3) {
-            unsigned long long hw, sw;
+            unsigned long long hw, hv, sw;
             long long base;
-            if (h0) { hw = h0; sw = TPX_SPECW(v0); base = i;
-                      *hi |= v0 & TPX_SWAR_HIGH; }
-            else if (h1) { hw = h1; sw = TPX_SPECW(v1); base = i + 8;
+            if (h0) { hw = h0; hv = v0; sw = TPX_SPECW(v0); base = i; }
+            else if (h1) { hw = h1; hv = v1; sw = TPX_SPECW(v1); base = i + 8;
                            sp_acc |= TPX_SPECW(v0);
-                           *hi |= (v0 | v1) & TPX_SWAR_HIGH; }
-            else if (h2) { hw = h2; sw = TPX_SPECW(v2); base = i + 16;
+                           *hi |= v0 & TPX_SWAR_HIGH; }
+            else if (h2) { hw = h2; hv = v2; sw = TPX_SPECW(v2); base = i + 16;
                            sp_acc |= TPX_SPECW(v0) | TPX_SPECW(v1);
-                           *hi |= (v0 | v1 | v2) & TPX_SWAR_HIGH; }
-            else { hw = h3; sw = TPX_SPECW(v3); base = i + 24;
+                           *hi |= (v0 | v1) & TPX_SWAR_HIGH; }
+            else { hw = h3; hv = v3; sw = TPX_SPECW(v3); base = i + 24;
                    sp_acc |= TPX_SPECW(v0) | TPX_SPECW(v1) | TPX_SPECW(v2);
-                   *hi |= (v0 | v1 | v2 | v3) & TPX_SWAR_HIGH; }
+                   *hi |= (v0 | v1 | v2) & TPX_SWAR_HIGH; }
             long long b = (__ffsll((long long)hw) - 1) / 8;
+            *hi |= hv & TPX_SWAR_HIGH & TPX_SWAR_UPTO(b);  // not past the hit
             sp_acc |= sw & ((b ? (1ULL << (8 * b)) : 1ULL) - 1);
             if (sp_acc) *spec = 1;
             return base + b;
@@ -1177,14 +1220,15 @@ __device__ __forceinline__ long long tpx_memchr_hi_spec(
     }
     for (; i + 8 <= n; i += 8) {
         unsigned long long v = *(const unsigned long long*)(p + i);
-        *hi |= v & TPX_SWAR_HIGH;
         unsigned long long hit = tpx_swar_zero(v ^ pat);
         if (hit) {
             long long b = (__ffsll((long long)hit) - 1) / 8;
+            *hi |= v & TPX_SWAR_HIGH & TPX_SWAR_UPTO(b);
             sp_acc |= TPX_SPECW(v) & ((b ? (1ULL << (8 * b)) : 1ULL) - 1);
             if (sp_acc) *spec = 1;
             return i + b;
         }
+        *hi |= v & TPX_SWAR_HIGH;
         sp_acc |= TPX_SPECW(v);
     }
     for (; i < n; ++i) {
