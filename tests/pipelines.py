@@ -519,6 +519,25 @@ def precompile_tests(verbose=False):
     # test_gpu_rtops stages (scalar-runtime device slice)
     from tests import rtops_pipelines
     n += rtops_pipelines.precompile(glib, _stage_compile)
+    # test_gpu_csv scan-edge files (one stage per distinct sniffed schema)
+    from tests import kern_models
+    from tests.test_gpu_csv import csv_edge_ident
+    seen = set()
+    for _name, data, valid in kern_models.csv_cases():
+        if not valid:
+            continue
+        _h, names, col_types = csvio.sniff(data[:1 << 20], [""], 0.9, None,
+                                           None, b",")
+        sp = plan.build_stage(col_types, names, [("map", csv_edge_ident)])
+        if not sp.compilable:
+            continue
+        src, desc = codegen.generate_stage(
+            sp, source="csv", sink="mem",
+            csv_info={"null_values": [""], "delimiter": ","})
+        if src not in seen:
+            seen.add(src)
+            _stage_compile(glib, src, desc)
+            n += 1
     return n
 
 

@@ -85,3 +85,36 @@ def test_csv_numeric_sniff_and_parse(tmp_path):
     ref = pyoracle_csv.run_csv_pipeline(data, [("map", add)])
     assert got == ref["output"]
     assert ds.exception_counts == ref["exception_counts"]
+
+
+def csv_edge_ident(x):
+    return (x["a"], x["b"], x["c"])
+
+
+def _edge_cases():
+    from tests import kern_models
+    return [(n, d) for n, d, valid in kern_models.csv_cases() if valid]
+
+
+@pytest.mark.parametrize("name,data", _edge_cases(),
+                         ids=[c[0] for c in _edge_cases()])
+def test_csv_scan_edge_files(tmp_path, name, data):
+    """The boundary-scan inputs of tests/test_gpu_kernels.py that are valid
+    CSV (quotes, "" pairs and quoted newlines on lane and 4 KB chunk edges,
+    rows longer than a chunk, CRLF, no trailing newline), end to end."""
+    path = _write(tmp_path, data)
+    ctx = tuplex_amd.Context()
+    ds = ctx.csv(path).map(csv_edge_ident)
+    got = ds.collect()
+    assert ds._last_outcome.mode == "gpu", ds._last_outcome.fallback_reason
+    ref = pyoracle_csv.run_csv_pipeline(data, [("map", csv_edge_ident)])
+    assert got == ref["output"]
+    assert ds.exception_counts == ref["exception_counts"]
+    # the cell values, against Python's csv module
+    import csv
+    import io
+    rows = list(csv.reader(io.StringIO(data.decode(), newline="")))[1:]
+    assert len(got) + sum(ds.exception_counts.values()) == len(rows)
+    if not ds.exception_counts:
+        assert [(str(a), b, str(c)) for a, b, c in got] == \
+            [tuple(r) for r in rows]

@@ -424,6 +424,27 @@ def test_aggregate_by_string_key_gpu():
     assert len(got) == len(codes)
 
 
+def test_aggregate_by_key_regrows_table_gpu():
+    """600 000 distinct i64 keys: more than half of the 1<<20 starting slots,
+    so run_core's regrow loop (tsize *= 8) runs once. Counts are exact."""
+    from tests.pipelines import aggby_comb, aggby_cnt
+    n_keys = 600000
+    rows = [(i * 7919 - 3, 0.5) for i in range(n_keys)]
+    rows += rows[:1000]              # the first thousand keys twice
+    rows.append((-1, 0.5))           # the table's empty marker as a real key
+    want = {k: 1 for k, _ in rows}
+    for k, _ in rows[:1000]:
+        want[k] = 2
+    assert len(want) == n_keys + 1 and len(want) * 2 > 1 << 20
+    ctx = tuplex_amd.Context()
+    ds = ctx.parallelize(rows, columns=["id", "volume"]).aggregateByKey(
+        aggby_comb, aggby_cnt, 0, ["id"])
+    got = ds.collect()
+    assert ds._last_outcome.mode == "gpu", ds._last_outcome.fallback_reason
+    assert len(got) == len(want)
+    assert dict(got) == want
+
+
 def test_unique_strings_gpu():
     import random
     rng = random.Random(19)

@@ -1095,10 +1095,14 @@ extern "C" __global__ void tpx_csv_select_counts(const long long* __restrict__ q
         rc[c] = (qscan[c] & 1) ? c1[c] : c0[c];
 }
 
-// row_lo/row_hi restrict emission to byte-chunks owning rows in [row_lo,row_hi)
-// so the offsets for one main-kernel chunk can be emitted just-in-time on that
-// chunk's stream (overlapping the previous chunk's main); chunks straddling a
-// range edge are re-emitted by the neighbouring call — idempotent writes.
+// row_lo/row_hi restrict emission to the byte-chunks that write
+// row_offs[row_lo..row_hi], which is what the main kernel for rows
+// [row_lo,row_hi) reads, so the offsets for one main-kernel chunk can be emitted
+// just-in-time on that chunk's stream (overlapping the previous chunk's main).
+// row_offs[row_lo] is the end of row row_lo-1: the byte-chunk holding that
+// newline is kept even when it is the chunk's last boundary (base[c+1] ==
+// row_lo), so one call suffices for its range. Chunks at a range edge are
+// re-emitted by the neighbouring call — idempotent writes.
 extern "C" __global__ void tpx_csv_emit_rows(const char* __restrict__ data,
                                              long long size, long long nchunks,
                                              const long long* __restrict__ qscan,
@@ -1114,7 +1118,7 @@ extern "C" __global__ void tpx_csv_emit_rows(const char* __restrict__ data,
     for (long long c = (long long)blockIdx.x * wpb + wid; c < nchunks;
          c += wstride) {
         if (base[c] >= row_hi) continue;
-        if (c + 1 < nchunks && base[c + 1] <= row_lo) continue;
+        if (c + 1 < nchunks && base[c + 1] < row_lo) continue;
         long long a = c * TPX_CSV_CHUNK + (long long)lane * TPX_CSV_LANE_BYTES;
         long long b = a + TPX_CSV_LANE_BYTES;
         if (a > size) a = size;
