@@ -151,7 +151,8 @@ struct tpx_stage {
     hipFunction_t k_main = nullptr, k_write = nullptr;
     hipFunction_t k_parse = nullptr;  // split mode (desc.split)
     hipFunction_t k_scan_block = nullptr, k_scan_add = nullptr;
-    hipFunction_t k_pair_total = nullptr;
+    hipFunction_t k_pair_scan_block = nullptr, k_pair_scan_sums = nullptr;
+    hipFunction_t k_pair_scan_add = nullptr;
     hipFunction_t k_csv_chunk = nullptr, k_csv_sel = nullptr, k_csv_rows = nullptr;
     hipFunction_t k_red_f64 = nullptr, k_red_f64_fin = nullptr;
     hipFunction_t k_red_i64 = nullptr, k_red_i64_fin = nullptr;
@@ -261,7 +262,9 @@ extern "C" tpx_stage* tpx_stage_compile(const char* hip_source,
         {"tpx_stage_write", &st->k_write, true},
         {"tpx_scan_block", &st->k_scan_block, true},
         {"tpx_scan_add", &st->k_scan_add, true},
-        {"tpx_pair_total", &st->k_pair_total, true},
+        {"tpx_pair_scan_block", &st->k_pair_scan_block, true},
+        {"tpx_pair_scan_sums", &st->k_pair_scan_sums, true},
+        {"tpx_pair_scan_add", &st->k_pair_scan_add, true},
         {"tpx_csv_chunk_stats", &st->k_csv_chunk, false},
         {"tpx_csv_select_counts", &st->k_csv_sel, false},
         {"tpx_csv_emit_rows", &st->k_csv_rows, false},
@@ -366,9 +369,10 @@ struct Persist {
 };
 static Persist g_persist[64];
 
-// two extra per-device streams for chunk pipelining (scans/writes of chunk c
-// overlap the main kernel of chunk c+1)
-static hipStream_t g_cstream[64][2];
+// three extra per-device streams for chunk pipelining: [0] and [1] alternate
+// the chunks' main kernels, each followed by its chunk's compaction scans;
+// [2] runs the chunk writes, which overlap the later chunks' main kernels
+static hipStream_t g_cstream[64][3];
 // small pinned staging area per device for tiny D2H reads (scan totals,
 // counters): pageable 8B copies cost a hidden staging hop each
 static void* g_pinned[64];
@@ -456,14 +460,13 @@ static int dev_scan(tpx_stage* st, hipStream_t stream, long long* d_in,
     if (launch(st->k_scan_block, (unsigned)nblocks, 256, stream, a1)) return -1;
     if (nblocks > 1) {
         ARENA_TAKE(sums_scan, (size_t)nblocks * 8);
-        long long dummy;
         if (dev_scan(st, stream, (long long*)sums, (long long*)sums_scan,
-                     nblocks, &dummy))
+                     nblocks, nullptr))
             return -1;
         void* a2[] = {&out_p, &sums_scan, &n};
         if (launch(st->k_scan_add, (unsigned)nblocks, 256, stream, a2)) return -1;
     }
-    if (!total) return 0;  // caller fetches totals itself (tpx_pair_total)
+    if (!total) return 0;  // caller does not need the total
     long long last_out = 0, last_in = 0;
     HIP_CHECK(hipMemcpyAsync(&last_out, d_out + (n - 1), 8,
                              hipMemcpyDeviceToHost, stream));
@@ -501,8 +504,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     EventPool& EP = g_events[dev];
     EP.reset();  // previous call's events are fully consumed by its return
     hipEvent_t ev1 = EP.get(), ev2 = EP.get(), ev3 = EP.get();
-    hipEvent_t evm0 = EP.get(), evm1 = EP.get(), evs1 = EP.get();
-    (void)evm1;
+    hipEvent_t evm0 = EP.get(), evs1 = EP.get();
     hipEventRecord(ev1, stream);
 
     // output columnar buffers (3 slots per column) from the arena
@@ -537,9 +539,11 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     }
     exc_cap = P.exc_cap_recs;
 
-    // chunk pipelining: split the rows into C ranges; each chunk's compaction
-    // scans + write kernel run on a side stream and overlap the NEXT chunk's
-    // main kernel (the step is otherwise strictly sequential; main dominates).
+    // chunk pipelining: split the rows into C ranges. Main kernels alternate
+    // between two side streams; chunk c's compaction scans are enqueued right
+    // behind main c on the same stream (ahead of main c+2), and its write
+    // kernel goes to a third stream once the host has read the chunk's totals
+    // — so scans and writes of chunk c run while mains c+1.. are in flight.
     // Aggregate sinks consume the full keep/outv arrays at once -> C=1.
     bool mem_sink = D.sink == "mem";
     int C = 1;
@@ -553,7 +557,12 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         C = env_c;
     }
     hipStream_t S[2] = {stream, stream};
-    if (C > 1) { S[0] = cstream(dev, 0); S[1] = cstream(dev, 1); }
+    hipStream_t SW = stream;  // chunk writes
+    if (C > 1) {
+        S[0] = cstream(dev, 0);
+        S[1] = cstream(dev, 1);
+        SW = cstream(dev, 2);
+    }
     // chunk split: sizes proportional to ratio^c (ratio<1 -> later chunks
     // smaller, shrinking the non-overlapped scan+write tail of the last chunk)
     static double env_ratio = [] {
@@ -712,11 +721,14 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
 
     void* d_exc_count = (char*)P.counters + 128;
     unsigned long long exc_count = 0;
-    // [m1, s0, s1, w0, w1] per chunk + 2 join events
-    std::vector<hipEvent_t> cev((size_t)C * 5 + 2);
+    // per chunk [main end = scans start, totals ready, write start, write end]
+    // + 3 join events
+    std::vector<hipEvent_t> cev((size_t)C * 4 + 3);
     for (auto& e : cev) e = EP.get();
+    void* d_keep_scan = nullptr;
+    void* d_size_scan = nullptr;
     long long total_rows = 0, total_bytes = 0;
-    long long chunk_rows[8] = {0}, chunk_bytes[8] = {0};
+    long long chunk_bytes[8] = {0};
     void* chunk_out[8] = {nullptr};
     void* d_out = nullptr;
     void* d_out_offs = nullptr;
@@ -726,6 +738,14 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         HIP_CHECK(hipMemsetAsync(P.counters, 0, 160, stream));
         hipEventRecord(evm0, stream);
         unsigned long long hs = heap_cap / (unsigned long long)C & ~255ull;
+        if (C > 1) {
+            d_out_offs = g_arena[dev].take(((size_t)n + 1) * 8);
+            d_out_rowidx = g_arena[dev].take(((size_t)n + 1) * 8);
+            d_keep_scan = g_arena[dev].take((size_t)n * 8);
+            d_size_scan = g_arena[dev].take((size_t)n * 8);
+            if (!d_out_offs || !d_out_rowidx || !d_keep_scan || !d_size_scan)
+                return -1;
+        }
         for (int c = 0; c < C; ++c) {
             hipStream_t sc = S[c & 1];
             if (C > 1) hipStreamWaitEvent(sc, evm0, 0);
@@ -767,52 +787,70 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
             } else {
                 if (launch(st->k_main, grid, 128, sc, args)) return -1;
             }
-            hipEventRecord(cev[(size_t)c * 5], sc);
-        }
-        // C>1 (non-agg sink): pipelined per-chunk scans + writes launched
-        // OPTIMISTICALLY before the overflow check (overflowed rows are marked
-        // exceptions with keep=false, so the write reads no garbage; on the
-        // rare overflow the attempt is simply redone)
-        if (C > 1) {
-            total_rows = total_bytes = 0;
-            d_out_offs = g_arena[dev].take(((size_t)n + 1) * 8);
-            d_out_rowidx = g_arena[dev].take(((size_t)n + 1) * 8);
-            void* d_keep_scan = g_arena[dev].take((size_t)n * 8);
-            void* d_size_scan = g_arena[dev].take((size_t)n * 8);
-            if (!d_out_offs || !d_out_rowidx || !d_keep_scan || !d_size_scan)
-                return -1;
-            for (int c = 0; c < C; ++c) {
-                hipStream_t sc = S[c & 1];
-                void* keep01_c = (char*)d_keep01 + cstart[c] * 8;
-                void* sizes_c = (char*)d_sizes + cstart[c] * 8;
+            hipEventRecord(cev[(size_t)c * 4], sc);
+            if (C > 1) {
+                // chunk c's compaction, in stream order right behind main c:
+                // fused pair scan of (keep01, sizes), then both totals into
+                // the chunk's own pinned slot; the host picks them up below
+                // without blocking this stream (main c+2 queues behind)
+                const long long BLOCK = 2048;  // TPX_SCAN_BLOCK
+                long long nblocks = (nc + BLOCK - 1) / BLOCK;
                 void* kscan_c = (char*)d_keep_scan + cstart[c] * 8;
                 void* sscan_c = (char*)d_size_scan + cstart[c] * 8;
-                long long rows_c = 0, bytes_c = 0;
-                hipEventRecord(cev[(size_t)c * 5 + 1], sc);
-                if (dev_scan(st, sc, (long long*)keep01_c,
-                             (long long*)kscan_c, ccnt[c], nullptr))
+                void* sums = g_arena[dev].take((size_t)nblocks * 16);
+                void* offs = g_arena[dev].take((size_t)nblocks * 16);
+                void* slot = g_arena[dev].take(16);
+                if (!sums || !offs || !slot) return -1;
+                void* a1[] = {&keep01_c, &sizes_c, &kscan_c, &sscan_c, &sums,
+                              &nc};
+                if (nblocks > 0 && launch(st->k_pair_scan_block,
+                                          (unsigned)nblocks, 256, sc, a1))
                     return -1;
-                if (dev_scan(st, sc, (long long*)sizes_c, (long long*)sscan_c,
-                             ccnt[c], nullptr))
+                void* a2[] = {&sums, &nblocks, &offs, &slot};
+                if (launch(st->k_pair_scan_sums, 1, 256, sc, a2)) return -1;
+                void* a3[] = {&kscan_c, &sscan_c, &offs, &nc};
+                if (nblocks > 1 && launch(st->k_pair_scan_add,
+                                          (unsigned)nblocks, 256, sc, a3))
                     return -1;
-                {   // both totals with one tiny kernel + one pinned D2H
-                    void* slot = g_arena[dev].take(16);
-                    if (!slot) return -1;
-                    void* ta[] = {&keep01_c, &kscan_c, &ccnt[c], &sizes_c,
-                                  &sscan_c, &ccnt[c], &slot};
-                    if (launch(st->k_pair_total, 1, 64, sc, ta)) return -1;
-                    long long* host = (long long*)pinned(dev);
-                    HIP_CHECK(hipMemcpyAsync(host, slot, 16,
-                                             hipMemcpyDeviceToHost, sc));
-                    HIP_CHECK(hipStreamSynchronize(sc));
-                    rows_c = host[0];
-                    bytes_c = host[1];
+                HIP_CHECK(hipMemcpyAsync((char*)pinned(dev) + 16 * c, slot, 16,
+                                         hipMemcpyDeviceToHost, sc));
+                hipEventRecord(cev[(size_t)c * 4 + 1], sc);
+            }
+        }
+        // C>1 (non-agg sink): per-chunk writes launched OPTIMISTICALLY before
+        // the overflow check (overflowed rows are marked exceptions with
+        // keep=false, so the write reads no garbage; on the rare overflow the
+        // attempt is simply redone). The host waits on each chunk's totals
+        // EVENT — not its stream, later mains are queued there — and launches
+        // the write on the write stream.
+        if (C > 1) {
+            total_rows = total_bytes = 0;
+            const long long hdr = mem_sink ? 8 : 0;
+            for (int c = 0; c < C; ++c) {
+                HIP_CHECK(hipEventSynchronize(cev[(size_t)c * 4 + 1]));
+                const long long* host =
+                    (const long long*)((char*)pinned(dev) + 16 * c);
+                long long rows_c = host[0], bytes_c = host[1];
+                if (c + 1 < C) {
+                    chunk_out[c] = g_arena[dev].take((size_t)bytes_c + 16);
+                    if (!chunk_out[c]) return -1;
+                } else {
+                    // last chunk: the grand total is known now, so it writes
+                    // straight at its place in the final buffer. The csv
+                    // writer's aligned 8-byte span stores assume an 8-aligned
+                    // chunk base, so the buffer itself starts off-alignment by
+                    // whatever puts this chunk's base on a multiple of 8.
+                    long long pad = (8 - ((hdr + total_bytes) & 7)) & 7;
+                    void* blk = g_arena[dev].take(
+                        (size_t)(pad + hdr + total_bytes + bytes_c) + 16);
+                    if (!blk) return -1;
+                    d_out = (char*)blk + pad;
+                    chunk_out[c] = (char*)d_out + hdr + total_bytes;
                 }
-                hipEventRecord(cev[(size_t)c * 5 + 2], sc);
-                chunk_out[c] = g_arena[dev].take((size_t)bytes_c + 16);
-                if (!chunk_out[c]) return -1;
-                long long out_byte0 = (mem_sink ? 8 : 0) + total_bytes;
+                long long out_byte0 = hdr + total_bytes;
                 void* keep_c = (char*)d_keep + cstart[c];
+                void* kscan_c = (char*)d_keep_scan + cstart[c] * 8;
+                void* sscan_c = (char*)d_size_scan + cstart[c] * 8;
                 void* offs_c = (char*)d_out_offs + total_rows * 8;
                 void* ridx_c = (char*)d_out_rowidx + total_rows * 8;
                 long long row0_c = row0 + cstart[c];
@@ -822,26 +860,36 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                 void* args[] = {&keep_c, &kscan_c, &sscan_c, &ccnt[c], &row0_c,
                                 &d_outv_c[c], &chunk_out[c], &offs_c, &ridx_c,
                                 &rows_c, &bytes_c, &out_byte0};
-                hipEventRecord(cev[(size_t)c * 5 + 3], sc);
-                if (launch(st->k_write, grid, 128, sc, args)) return -1;
-                hipEventRecord(cev[(size_t)c * 5 + 4], sc);
-                chunk_rows[c] = rows_c;
+                hipStreamWaitEvent(SW, cev[(size_t)c * 4 + 1], 0);
+                hipEventRecord(cev[(size_t)c * 4 + 2], SW);
+                if (launch(st->k_write, grid, 128, SW, args)) return -1;
+                hipEventRecord(cev[(size_t)c * 4 + 3], SW);
                 chunk_bytes[c] = bytes_c;
                 total_rows += rows_c;
                 total_bytes += bytes_c;
             }
+            // gather chunks 0..C-2 into the final buffer; the main streams are
+            // idle by now, so these copies overlap the last chunk's write
+            long long acc = hdr;
+            for (int c = 0; c + 1 < C; ++c) {
+                if (chunk_bytes[c]) {
+                    hipStreamWaitEvent(S[c & 1], cev[(size_t)c * 4 + 3], 0);
+                    HIP_CHECK(hipMemcpyAsync((char*)d_out + acc, chunk_out[c],
+                                             (size_t)chunk_bytes[c],
+                                             hipMemcpyDeviceToDevice,
+                                             S[c & 1]));
+                }
+                acc += chunk_bytes[c];
+            }
         }
-        // overflow check (all mains have completed: each chunk's scans synced
-        // its stream for C>1; explicit sync below covers C==1)
+        // overflow check (all mains have completed: for C>1 the host has seen
+        // every chunk's totals event, recorded behind its main; the stream
+        // sync below covers C==1)
         unsigned long long* counters =
             (unsigned long long*)((char*)pinned(dev) + 256);
         HIP_CHECK(hipMemcpyAsync(counters, P.counters, 160,
                                  hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        if (C == 1) {
-            // the copy above raced the main kernel only through stream order
-            // (same stream) -> already correct
-        }
         unsigned long long max_used = 0;
         for (int c = 0; c < C; ++c)
             max_used = std::max(max_used, counters[c * 2]);
@@ -853,6 +901,13 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
             break;
         }
         if (attempt >= 3) { set_err("retry limit (heap/exc overflow)"); return -1; }
+        if (C > 1) {
+            // the optimistic writes and gather copies of this attempt still
+            // use the buffers the next attempt rewrites (and may free)
+            HIP_CHECK(hipStreamSynchronize(S[0]));
+            HIP_CHECK(hipStreamSynchronize(S[1]));
+            HIP_CHECK(hipStreamSynchronize(SW));
+        }
         if (heap_overflow) {
             (void)hipFree(P.heap);
             P.heap = nullptr;
@@ -1103,29 +1158,21 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     } else {
     long long out_total;
     if (sink_done) {
-        // C>1: per-chunk writes already done; gather the chunk buffers into
-        // the final contiguous output
+        // C>1: the chunk writes and gather copies are already enqueued; join
+        // the side streams back into `stream`
         out_total = (mem_sink ? 8 : 0) + total_bytes;
-        d_out = g_arena[dev].take((size_t)out_total + 16);
-        if (!d_out) return -1;
-        long long acc = mem_sink ? 8 : 0;
-        for (int c = 0; c < C; ++c) {
-            if (chunk_bytes[c])
-                HIP_CHECK(hipMemcpyAsync((char*)d_out + acc, chunk_out[c],
-                                         (size_t)chunk_bytes[c],
-                                         hipMemcpyDeviceToDevice, S[c & 1]));
-            acc += chunk_bytes[c];
-        }
-        // join the side streams back into `stream`
-        hipEventRecord(cev[(size_t)C * 5], S[0]);
-        hipEventRecord(cev[(size_t)C * 5 + 1], S[1]);
-        hipStreamWaitEvent(stream, cev[(size_t)C * 5], 0);
-        hipStreamWaitEvent(stream, cev[(size_t)C * 5 + 1], 0);
+        hipEventRecord(cev[(size_t)C * 4], S[0]);
+        hipEventRecord(cev[(size_t)C * 4 + 1], S[1]);
+        hipEventRecord(cev[(size_t)C * 4 + 2], SW);
+        hipStreamWaitEvent(stream, cev[(size_t)C * 4], 0);
+        hipStreamWaitEvent(stream, cev[(size_t)C * 4 + 1], 0);
+        hipStreamWaitEvent(stream, cev[(size_t)C * 4 + 2], 0);
         hipEventRecord(evs1, stream);
     } else {
         // C==1: compaction scans + one write into the final buffer
-        ARENA_TAKE(d_keep_scan, (size_t)n * 8);
-        ARENA_TAKE(d_size_scan, (size_t)n * 8);
+        d_keep_scan = g_arena[dev].take((size_t)n * 8);
+        d_size_scan = g_arena[dev].take((size_t)n * 8);
+        if (!d_keep_scan || !d_size_scan) return -1;
         if (dev_scan(st, stream, (long long*)d_keep01, (long long*)d_keep_scan,
                      n, &total_rows))
             return -1;
@@ -1244,18 +1291,18 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     // main: shared start -> latest chunk-main end (spans both side streams)
     float tmain = 0;
     for (int c = 0; c < C; ++c) {
-        hipEventElapsedTime(&ms, evm0, cev[(size_t)c * 5]);
+        hipEventElapsedTime(&ms, evm0, cev[(size_t)c * 4]);
         tmain = std::max(tmain, ms);
     }
     res->t_main_ms = tmain;
     if (sink_done) {
         float tc = 0, tw = 0;
         for (int c = 0; c < C; ++c) {
-            hipEventElapsedTime(&ms, cev[(size_t)c * 5 + 1],
-                                cev[(size_t)c * 5 + 2]);
+            hipEventElapsedTime(&ms, cev[(size_t)c * 4],
+                                cev[(size_t)c * 4 + 1]);
             tc += ms;
-            hipEventElapsedTime(&ms, cev[(size_t)c * 5 + 3],
-                                cev[(size_t)c * 5 + 4]);
+            hipEventElapsedTime(&ms, cev[(size_t)c * 4 + 2],
+                                cev[(size_t)c * 4 + 3]);
             tw += ms;
         }
         res->t_compact_ms = tc;
@@ -1388,8 +1435,7 @@ static int64_t csv_boundary_and_core(tpx_stage* st, void* d_in_p, long long size
                         &quotes_on};
         if (launch(st->k_csv_chunk, grid_w, 256, stream, args)) return -1;
     }
-    long long qtotal = 0;
-    if (dev_scan(st, stream, (long long*)d_q, (long long*)d_qs, nchunks, &qtotal))
+    if (dev_scan(st, stream, (long long*)d_q, (long long*)d_qs, nchunks, nullptr))
         return -1;
     {
         void* args[] = {&d_qs, &d_c0, &d_c1, &d_rc, &nchunks};

@@ -1859,4 +1859,110 @@ extern "C" __global__ void tpx_scan_add(long long* __restrict__ data,
         if (i < n) data[i] += add;
     }
 }
+
+// fused pair scan: the chunk compaction scans TWO i64 arrays of equal length
+// (keep01 -> row index, sizes -> byte offset). Three launches do both: per-block
+// scan of both arrays, ONE block scanning the interleaved block sums serially
+// (tiled with a running carry; no inter-block waiting of any kind), add pass.
+// sums/offs hold nblocks (a, b) pairs; slot[0..1] receive the grand totals.
+extern "C" __global__ void tpx_pair_scan_block(const long long* __restrict__ a_in,
+                                               const long long* __restrict__ b_in,
+                                               long long* __restrict__ a_out,
+                                               long long* __restrict__ b_out,
+                                               long long* __restrict__ sums,
+                                               long long n) {
+    __shared__ long long sha[TPX_SCAN_THREADS];
+    __shared__ long long shb[TPX_SCAN_THREADS];
+    long long base = (long long)blockIdx.x * TPX_SCAN_BLOCK;
+    long long va[TPX_SCAN_ITEMS], vb[TPX_SCAN_ITEMS];
+    long long suma = 0, sumb = 0;
+    #pragma unroll
+    for (int k = 0; k < TPX_SCAN_ITEMS; ++k) {
+        long long i = base + threadIdx.x * TPX_SCAN_ITEMS + k;
+        va[k] = (i < n) ? a_in[i] : 0;
+        vb[k] = (i < n) ? b_in[i] : 0;
+        suma += va[k];
+        sumb += vb[k];
+    }
+    sha[threadIdx.x] = suma;
+    shb[threadIdx.x] = sumb;
+    __syncthreads();
+    for (int off = 1; off < TPX_SCAN_THREADS; off <<= 1) {
+        long long ua = (threadIdx.x >= off) ? sha[threadIdx.x - off] : 0;
+        long long ub = (threadIdx.x >= off) ? shb[threadIdx.x - off] : 0;
+        __syncthreads();
+        sha[threadIdx.x] += ua;
+        shb[threadIdx.x] += ub;
+        __syncthreads();
+    }
+    if (threadIdx.x == TPX_SCAN_THREADS - 1) {
+        sums[2 * (long long)blockIdx.x] = sha[TPX_SCAN_THREADS - 1];
+        sums[2 * (long long)blockIdx.x + 1] = shb[TPX_SCAN_THREADS - 1];
+    }
+    long long runa = sha[threadIdx.x] - suma;
+    long long runb = shb[threadIdx.x] - sumb;
+    #pragma unroll
+    for (int k = 0; k < TPX_SCAN_ITEMS; ++k) {
+        long long i = base + threadIdx.x * TPX_SCAN_ITEMS + k;
+        if (i < n) {
+            a_out[i] = runa;
+            b_out[i] = runb;
+        }
+        runa += va[k];
+        runb += vb[k];
+    }
+}
+
+// launched as ONE block of TPX_SCAN_THREADS threads
+extern "C" __global__ void tpx_pair_scan_sums(const long long* __restrict__ sums,
+                                              long long nblocks,
+                                              long long* __restrict__ offs,
+                                              long long* __restrict__ slot) {
+    __shared__ long long sha[TPX_SCAN_THREADS];
+    __shared__ long long shb[TPX_SCAN_THREADS];
+    long long carrya = 0, carryb = 0;
+    for (long long t0 = 0; t0 < nblocks; t0 += TPX_SCAN_THREADS) {
+        long long i = t0 + threadIdx.x;
+        long long a = (i < nblocks) ? sums[2 * i] : 0;
+        long long b = (i < nblocks) ? sums[2 * i + 1] : 0;
+        sha[threadIdx.x] = a;
+        shb[threadIdx.x] = b;
+        __syncthreads();
+        for (int off = 1; off < TPX_SCAN_THREADS; off <<= 1) {
+            long long ua = (threadIdx.x >= off) ? sha[threadIdx.x - off] : 0;
+            long long ub = (threadIdx.x >= off) ? shb[threadIdx.x - off] : 0;
+            __syncthreads();
+            sha[threadIdx.x] += ua;
+            shb[threadIdx.x] += ub;
+            __syncthreads();
+        }
+        if (i < nblocks) {
+            offs[2 * i] = carrya + sha[threadIdx.x] - a;
+            offs[2 * i + 1] = carryb + shb[threadIdx.x] - b;
+        }
+        carrya += sha[TPX_SCAN_THREADS - 1];
+        carryb += shb[TPX_SCAN_THREADS - 1];
+        __syncthreads();  // tile totals read before the next tile overwrites
+    }
+    if (threadIdx.x == 0) {
+        slot[0] = carrya;
+        slot[1] = carryb;
+    }
+}
+
+extern "C" __global__ void tpx_pair_scan_add(long long* __restrict__ a_out,
+                                             long long* __restrict__ b_out,
+                                             const long long* __restrict__ offs,
+                                             long long n) {
+    long long base = (long long)blockIdx.x * TPX_SCAN_BLOCK;
+    long long adda = offs[2 * (long long)blockIdx.x];
+    long long addb = offs[2 * (long long)blockIdx.x + 1];
+    for (int k = 0; k < TPX_SCAN_ITEMS; ++k) {
+        long long i = base + threadIdx.x + (long long)k * TPX_SCAN_THREADS;
+        if (i < n) {
+            a_out[i] += adda;
+            b_out[i] += addb;
+        }
+    }
+}
 #endif  // TPX_HOST_TEST

@@ -52,7 +52,7 @@ DEFAULTS = {
     "tuplex.gpu.stagingBufferSize": "256MB",
     # GPU range granularity: the reference splits at 64MB for CPU-thread
     # work distribution (ContextOptions.cc:227); one MI355X wants fewer,
-    # larger ranges (the C-ABI pipelines 4 sub-chunks on 2 streams per call)
+    # larger ranges (the C-ABI pipelines 4 sub-chunks on 3 streams per call)
     "tuplex.gpu.inputSplitSize": "256MB",
     "tuplex.gpu.heapFactor": "2.0",
     "tuplex.gpu.devices": "1",            # in-process device fan-out (N>1 opt-in; 0 = all visible)
