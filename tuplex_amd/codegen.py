@@ -52,6 +52,18 @@ def regex_header() -> str:
     return _RE_HEADER_CACHE
 
 
+_FMT_HEADER_CACHE = None
+
+
+def fmt_header() -> str:
+    global _FMT_HEADER_CACHE
+    if _FMT_HEADER_CACHE is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                            "csrc", "tpx_fmt.hip.h")
+        _FMT_HEADER_CACHE = open(path).read()
+    return _FMT_HEADER_CACHE
+
+
 def _ctype(t):
     base = T.deopt(t)
     if base in (T.I64,):
@@ -138,6 +150,9 @@ class StageCodegen:
         self.lits = {}  # python str -> lit var name
         self.lit_defs = []
         self.join_defs = []   # embedded hash-join build tables (per join op)
+        self.fmt_progs = {}   # format template items -> (array, count, blob)
+        self.fmt_defs = []
+        self.uses_fmt = False  # a format/capwords node: append tpx_fmt.hip.h
         # multi-needle scan fusion: pass 1 registers every const-needle
         # find/contains per structurally-identified haystack; pass 2 emits ONE
         # SWAR window scan per group (the serial dependent-load chains of
@@ -193,6 +208,21 @@ class StageCodegen:
             self.re_defs.append("__device__ const int %s[%d] = {%s};"
                                 % (name, len(key), ",".join(map(str, key))))
         return self.re_progs[key]
+
+    def fmt_prog(self, items) -> Tuple[str, int, str]:
+        """Embed a parsed format template (udf/fmtspec.py) once per stage;
+        returns (array name, item count, literal blob pointer)."""
+        from .udf import fmtspec
+        self.uses_fmt = True
+        key = tuple(items)
+        if key not in self.fmt_progs:
+            words, blob = fmtspec.encode(items)
+            name = "fmt_prog%d" % len(self.fmt_progs)
+            self.fmt_defs.append("__device__ const int %s[%d] = {%s};"
+                                 % (name, len(words), ",".join(map(str, words))))
+            self.fmt_progs[key] = (name, len(items),
+                                   self.lit(blob.decode("utf-8")) + ".p")
+        return self.fmt_progs[key]
 
     @staticmethod
     def _struct_key(node):
@@ -849,6 +879,47 @@ class StageCodegen:
                 em.w("bool %s_n = %s[%d] < 0;" % (r, cp, 2 * n["w"]))
                 return (r, r + "_n")
             return (r, None)
+        if op == "truthy":
+            # CPython truth value; a null Option is false (reads the flag,
+            # never raises)
+            x, nx = ev(a[0])
+            base = T.deopt(a[0]["t"])
+            test = {T.I64: "(%s) != 0", T.F64: "(%s) != 0.0",
+                    T.STR: "(%s).n > 0", T.BOOL: "(%s)"}[base] % x
+            if nx is not None and nx != "false":
+                test = "!(%s) && (%s)" % (nx, test)
+            r = em.fresh("b")
+            em.w("bool %s = %s;" % (r, test))
+            return (r, None)
+        if op == "format":
+            prog, nitems, lits = self.fmt_prog(n["v"])
+            text_args = {it[1] for it in n["v"] if it[0] == "bool"}
+            fa = em.fresh("fa")
+            em.w("TpxFmtArg %s[%d];" % (fa, len(a)))
+            for k, arg in enumerate(a):
+                x, _ = ev(arg)
+                if arg["t"] == T.STR:
+                    em.w("%s[%d].p = (%s).p; %s[%d].n = (%s).n;"
+                         % (fa, k, x, fa, k, x))
+                elif k in text_args:
+                    em.w("%s[%d].p = tpx_str_bool(%s).p; "
+                         "%s[%d].n = tpx_str_bool(%s).n;"
+                         % (fa, k, x, fa, k, x))
+                else:
+                    em.w("%s[%d].p = nullptr; %s[%d].n = (long long)(%s);"
+                         % (fa, k, fa, k, x))
+            r = em.fresh("s")
+            em.w("tstr %s = tpx_format(heap, %s, %d, %s, %s, &_ec);"
+                 % (r, prog, nitems, lits, fa))
+            self._check(em, opid)
+            return (r, None)
+        if op == "capwords":
+            x, _ = ev(a[0])
+            self.uses_fmt = True
+            r = em.fresh("s")
+            em.w("tstr %s = tpx_capwords(heap, %s, &_ec);" % (r, x))
+            self._check(em, opid)
+            return (r, None)
         if op == "fmt_int":
             x, _ = ev(a[0])
             r = em.fresh("s")
@@ -1223,8 +1294,20 @@ class StageCodegen:
             return self._qfree_node(a[0], env)
         if op == "re_group":  # a view into the match's subject string
             return self._qfree_node(a[0]["args"][0], env)
-        if op == "re_matched":
+        if op in ("re_matched", "truthy"):
             return True
+        if op == "capwords":  # letters change case, whitespace becomes ' '
+            return self._qfree_node(a[0], env)
+        if op == "format":
+            # every literal segment statically clean AND every str argument;
+            # int/bool fields and the padding are digits, letters, '-', ' '
+            q = True
+            for it in n["v"]:
+                if it[0] == "lit":
+                    q = self._qfree_and(q, self._qfree_static_str(it[1]))
+                elif it[0] == "str":
+                    q = self._qfree_and(q, self._qfree_node(a[it[1]], env))
+            return q
         if op == "concat":
             return self._qfree_and(self._qfree_node(a[0], env),
                                    self._qfree_node(a[1], env))
@@ -1400,7 +1483,8 @@ class StageCodegen:
             "// generated by tuplex_amd.codegen — stage %s" % sp.signature(),
             runtime_header(),
             "",
-        ] + self._re_section() + self.lit_defs + self.join_defs + [
+        ] + self._re_section() + self._fmt_section() + self.lit_defs + \
+            self.join_defs + [
             "",
             "struct Out {",
         ] + out_fields + [
@@ -1425,6 +1509,13 @@ class StageCodegen:
         if not getattr(self, "re_defs", None):
             return []
         return [regex_header(), ""] + self.re_defs
+
+    def _fmt_section(self):
+        """String-builder header + embedded templates — only for stages with a
+        format or capwords node (same reasoning as _re_section)."""
+        if not self.uses_fmt:
+            return []
+        return [fmt_header(), ""] + self.fmt_defs
 
     def _process_signature(self, in_types):
         params = []

@@ -14,6 +14,14 @@ Supported expressions: constants, names, bin/bool/unary ops, chained comparisons
 endswith/swapcase), len/int/float/str/abs, subscript (column access, str index,
 str slice), '%0Nd' % x format, tuple literals (return position only).
 
+Truth values: in a condition position (if/elif test, conditional test, `not`
+operand, and/or inside those) an i64/f64/str value or an Option of one takes
+CPython's truth value; a null Option is false. `a or b` as a VALUE is outside.
+Membership: `e in [c1, ..]` / `(c1, ..)` / `not in` over 1..32 constants, all
+str or all numbers. Formatting: S.format(..) and S % (..) with a constant S
+(udf/fmtspec.py has the subset); a lone %d / %0Nd / %s keeps its own nodes.
+string.capwords(s) with one argument, `string` being the real module.
+
 Regular expressions: re.search(P, s) / re.match(P, s) / re.fullmatch(P, s) with
 exactly two arguments, where `re` is the real module (global or closure) and P
 folds to a compile-time str (literal, global/closure constant, a local bound
@@ -29,10 +37,12 @@ AttributeError, as in CPython.
 import ast
 import inspect
 import re as _re_module
+import string as _string_module
 import textwrap
 from typing import Callable, Dict, List, Optional
 
 from .. import ttypes as T
+from . import fmtspec
 from . import relower
 from . import tir
 
@@ -221,8 +231,9 @@ class _Compiler:
     def _cond(self, e, env):
         """`e` in a truth-value position (if/elif test, conditional test, `not`
         operand, and/or operands inside one of those): a match value lowers to
-        an explicit re_matched() BOOL node here, so tir.ifexpr/notop/boolop
-        keep insisting on BOOL."""
+        an explicit re_matched() BOOL node here, any other non-bool value to
+        truthy() (CPython's truth value; a null Option is false, not an
+        error), so tir.ifexpr/notop/boolop keep insisting on BOOL."""
         if isinstance(e, ast.BoolOp):
             op = "and" if isinstance(e.op, ast.And) else "or"
             node = self._cond(e.values[0], env)
@@ -231,10 +242,7 @@ class _Compiler:
             return node
         if isinstance(e, ast.UnaryOp) and isinstance(e.op, ast.Not):
             return tir.notop(self._cond(e.operand, env))
-        node = self._expr(e, env)
-        if node["t"] == tir.MATCH:
-            return tir.re_matched(node)
-        return node
+        return tir.truthy(self._expr(e, env))
 
     def _const_str(self, e, env):
         """Fold `e` to a compile-time str (regex patterns), else None."""
@@ -258,6 +266,48 @@ class _Compiler:
     def _is_re_module(self, e, env):
         return (isinstance(e, ast.Name) and e.id not in env
                 and self.globals.get(e.id) is _re_module)
+
+    def _is_string_module(self, e, env):
+        return (isinstance(e, ast.Name) and e.id not in env
+                and self.globals.get(e.id) is _string_module)
+
+    def _string_call(self, e, env):
+        if e.func.attr != "capwords":
+            raise UDFCompileError("unsupported function string.%s"
+                                  % e.func.attr)
+        if len(e.args) != 1 or e.keywords:
+            raise UDFCompileError("string.capwords takes exactly (s); a sep "
+                                  "argument is not supported")
+        return tir.capwords(self._no_match_arg(self._expr(e.args[0], env)))
+
+    @staticmethod
+    def _no_match_arg(node):
+        if node["t"] == tir.MATCH:
+            raise UDFCompileError("a match object cannot be an argument")
+        return node
+
+    def _membership(self, subject, seq, env, negate):
+        """`e in [c1, ..]` / `e in (c1, ..)` over compile-time constants: an or
+        chain of the equality nodes the device already runs. A null Option
+        subject compares unequal to every element (None in ["a"] is False)."""
+        self._no_match_arg(subject)
+        if not (1 <= len(seq.elts) <= 32):
+            raise UDFCompileError("constant membership needs 1 to 32 elements")
+        consts = []
+        for el in seq.elts:
+            c = self._expr(el, env)
+            if c["op"] != "const" or c.get("v") is None:
+                raise UDFCompileError("membership elements must be str or "
+                                      "number constants")
+            consts.append(c)
+        n_str = sum(isinstance(c["v"], str) for c in consts)
+        if n_str not in (0, len(consts)):
+            raise UDFCompileError("membership list mixes str and numbers")
+        node = None
+        for c in consts:
+            eq = tir.binop("eq", subject, c)
+            node = eq if node is None else tir.boolop("or", node, eq)
+        return tir.notop(node) if negate else node
 
     def _re_call(self, e, env):
         mode = e.func.attr
@@ -324,6 +374,13 @@ class _Compiler:
             left = self._expr(e.left, env)
             result = None
             for op, comp in zip(e.ops, e.comparators):
+                if isinstance(op, (ast.In, ast.NotIn)) and isinstance(
+                        comp, (ast.List, ast.Tuple)):
+                    if len(e.ops) != 1:
+                        raise UDFCompileError("chained comparison through a "
+                                              "constant sequence")
+                    return self._membership(left, comp, env,
+                                            isinstance(op, ast.NotIn))
                 right = self._expr(comp, env)
                 c = self._cmp_ast(op, left, right)
                 result = c if result is None else tir.boolop("and", result, c)
@@ -353,17 +410,38 @@ class _Compiler:
 
     def _fmt(self, e, env):
         spec = e.left.value
-        arg = self._expr(e.right, env)
-        # subset: single %d / %0Nd / %s directive
+        # a lone %d / %0Nd / %s directive keeps its dedicated nodes
         import re
         m = re.fullmatch(r"%0(\d+)d", spec)
-        if m:  # '%05d' -> zero-padded width N
-            return tir.fmt(int(m.group(1)), arg)
-        if spec == "%d":
-            return tir.fmt(0, arg)
-        if spec == "%s":
+        if m or spec in ("%d", "%s"):
+            arg = self._expr(e.right, env)
+            if m:  # '%05d' -> zero-padded width N
+                return tir.fmt(int(m.group(1)), arg)
+            if spec == "%d":
+                return tir.fmt(0, arg)
             return tir.call("to_str", [arg])
-        raise UDFCompileError("unsupported format spec %r" % spec)
+        elts = e.right.elts if isinstance(e.right, ast.Tuple) else [e.right]
+        return self._format(spec, [self._expr(a, env) for a in elts],
+                            fmtspec.parse_percent)
+
+    def _format(self, template, args, parse):
+        """Constant template + argument nodes -> one `format` node (a template
+        without fields folds to a constant)."""
+        kinds = []
+        for a in args:
+            self._no_match_arg(a)
+            k = {T.I64: "i", T.BOOL: "b", T.STR: "s"}.get(T.deopt(a["t"]))
+            if k is None:
+                raise UDFCompileError("format argument of type %r is not "
+                                      "supported" % (a["t"],))
+            kinds.append(k)
+        try:
+            items = parse(template, kinds)
+        except fmtspec.FmtError as ex:
+            raise UDFCompileError(str(ex))
+        if not args:
+            return tir.const("".join(it[1] for it in items))
+        return tir.format(items, args)
 
     def _binop_ast(self, op, a, b):
         m = {ast.Add: "add", ast.Sub: "sub", ast.Mult: "mul", ast.Div: "truediv",
@@ -402,6 +480,20 @@ class _Compiler:
         if isinstance(e.func, ast.Attribute):
             if self._is_re_module(e.func.value, env):
                 return self._re_call(e, env)
+            if self._is_string_module(e.func.value, env):
+                return self._string_call(e, env)
+            if e.func.attr == "format":
+                template = self._const_str(e.func.value, env)
+                if template is None:
+                    raise UDFCompileError(".format needs a compile-time "
+                                          "template string")
+                if e.keywords or any(isinstance(a, ast.Starred)
+                                     for a in e.args):
+                    raise UDFCompileError(".format takes positional "
+                                          "arguments only")
+                return self._format(template,
+                                    [self._expr(a, env) for a in e.args],
+                                    fmtspec.parse_format)
             obj = self._expr(e.func.value, env)
             meth = e.func.attr
             args = [self._expr(a, env) for a in e.args]

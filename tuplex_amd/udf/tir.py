@@ -106,6 +106,22 @@ def notop(a):
     return mk("not", T.BOOL, [a])
 
 
+def truthy(a):
+    """CPython truth value of a non-bool in a condition position: i64/f64
+    nonzero (nan is true, -0.0 false), str non-empty; an Option is false when
+    null — the node reads the null flag itself, it never unwraps."""
+    t = a["t"]
+    if t == T.BOOL:
+        return a
+    if t == T.NULL:
+        return const(False)
+    if t == MATCH:
+        return re_matched(a)
+    if T.deopt(t) not in (T.I64, T.F64, T.STR, T.BOOL):
+        raise TirError("no truth value for %r" % (t,))
+    return mk("truthy", T.BOOL, [a])
+
+
 def neg(a):
     a = _deopt_node(a)
     if a["t"] not in _NUM:
@@ -219,6 +235,26 @@ def fmt(spec, arg):
     if arg["t"] not in (T.I64, T.BOOL):
         raise TirError("fmt %d needs int")
     return mk("fmt_int", T.STR, [arg], w=spec)
+
+
+def format(items, args):
+    """S.format(...) / S % (...) with a constant template (udf/fmtspec.py).
+    `items` — the literal segments and field descriptors — live in `v` (CSE
+    key, stage signature); `args` are the unwrapped I64/BOOL/STR values, so
+    column lineage sees exactly what the template reads."""
+    args = [_deopt_node(a) for a in args]
+    for a in args:
+        if a["t"] not in (T.I64, T.BOOL, T.STR):
+            raise TirError("format argument of type %r" % (a["t"],))
+    return mk("format", T.STR, args, v=tuple(items))
+
+
+def capwords(s):
+    """string.capwords(s), one-argument form."""
+    s = _deopt_node(s)
+    if s["t"] != T.STR:
+        raise TirError("capwords on non-str")
+    return mk("capwords", T.STR, [s])
 
 
 # Result of re.search/re.match/re.fullmatch with a constant pattern. Internal to
