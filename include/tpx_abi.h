@@ -104,8 +104,10 @@ typedef struct {
     /* per-phase kernel timings (HIP events on the launch stream) */
     double   t_boundary_ms;   /* csv row-boundary scan kernels */
     double   t_main_ms;       /* fused parse+UDF stage kernel (dominant) */
-    double   t_compact_ms;    /* prefix-sum compaction */
-    double   t_write_ms;      /* serialize / csv-format kernel */
+    double   t_compact_ms;    /* prefix-sum compaction (fused csv sink: the
+                                 scan over the per-batch descriptors) */
+    double   t_write_ms;      /* serialize / csv-format kernel (fused csv
+                                 sink: tpx_csv_gather) */
     int64_t  in_num_rows;     /* input rows seen by the stage */
 } tpx_result;
 

@@ -184,6 +184,9 @@ class StageCodegen:
         # a dense park cost more than the UDF kernel's occupancy win
         # returned); 1 = dense byte park (kept for experiments)
         self.park_copy = _os.environ.get("TPX_PARK_COPY", "0") == "1"
+        # fused csv sink: decided in generate(), once the stage's shape is known
+        self.fused = False
+        self.fused_window = False
 
     # ---- literals -----------------------------------------------------------
     def lit(self, s: str) -> str:
@@ -1467,13 +1470,38 @@ class StageCodegen:
         # generate kernels BEFORE assembling (they may add string literals)
         self.store_types = store_types
         self.full_out_types = out_types
+        # Fused csv sink: the LDS-staged main kernel formats kept rows itself
+        # (per-wave commit into a text scratch + tpx_csv_gather) instead of
+        # storing columnar slots for tpx_stage_write. Not for the columnar
+        # source, split mode, the terminal duplicate-key join or aggregates.
+        # TPX_FUSED_SINK=0 emits the two-pass source and description; like
+        # TPX_MAIN_LB and TPX_GEN_BODY it is read here, at codegen time, so
+        # the two builds have different sources (= cache keys).
+        import os as _os
+        self.fused = (self.sink == "csv" and self.source != "col"
+                      and not self.split and dup_op is None
+                      and getattr(sp, "agg_expr", None) is None
+                      and _os.environ.get("TPX_FUSED_SINK", "1") != "0"
+                      and _os.environ.get("TPX_GEN_BODY") != "1")
+        # Kept lanes format into a per-wave LDS output window (WRITE_CAP
+        # bytes, as tpx_stage_write does) that the wave then copies to its
+        # region with aligned 8-byte stores; TPX_FUSED_WINDOW=0 formats
+        # straight to global memory instead. Measured on Zillow Z1: window
+        # 863-873, direct 834-837, two-pass 815-818 M rows/s (profiles/
+        # README.md, round 4). The window makes the block 40 KiB; Z1's kernel
+        # holds 4 blocks/CU by registers either way, a stage small enough
+        # for 5 blocks of 32 KiB gives one up.
+        self.fused_window = (self.fused and
+                             _os.environ.get("TPX_FUSED_WINDOW", "1") != "0")
         if self.split:
             main_src = ("#define TPX_SPAN_CAP %d\n" % self.SPAN_CAP +
                         self._parse_kernel(in_types) + "\n\n" +
                         self._main_kernel_split(in_types, store_types))
         else:
             main_src = self._main_kernel(in_types, store_types)
-        if dup_op is None:
+        if self.fused:
+            write_src = ""  # no tpx_stage_write: run_core gathers instead
+        elif dup_op is None:
             write_src = self._write_kernel(out_types)
         elif self.sink == "mem":
             write_src = self._write_kernel_mem_dup(out_types, store_types)
@@ -1536,10 +1564,13 @@ class StageCodegen:
     # 2048 threads x ~200 B rows >> 32 KiB L1 per CU). Waves whose span exceeds
     # TPX_SPAN_CAP fall back to parsing from global memory (rare: long rows).
     # bytes per wave: 2 waves/block stage 2*CAP+80 B of LDS; 16344 keeps the
-    # block at exactly 32768 B so FIVE blocks fit the 160 KiB CU budget ->
-    # 10 waves/CU (at 16384+pad the block tips over 32 KiB and occupancy
-    # drops to 4 blocks = 8 waves/CU). The 80-B tail absorbs the mask walk's
-    # aligned 64-B group overread past the last row of a wave's span.
+    # block at exactly 32768 B, so by LDS alone FIVE blocks fit the 160 KiB CU
+    # budget (10 waves/CU). For a stage as large as Zillow Z1 registers are the
+    # tighter limit: its code object allocates 256 registers per lane
+    # (.vgpr_count 256: 128 VGPRs plus 128 that hold spills), i.e. 2
+    # waves/SIMD = 8 waves/CU = 4 blocks (profiles/README.md, round 4). Small
+    # stages stay LDS-limited at 5 blocks. The 80-B tail absorbs the mask
+    # walk's aligned 64-B group overread past the last row of a wave's span.
     SPAN_CAP = 16344
 
     def _main_kernel(self, in_types, out_types):
@@ -1547,10 +1578,11 @@ class StageCodegen:
             return self._main_kernel_col(in_types, out_types)
         L = []
         L.append("#define TPX_SPAN_CAP %d" % self.SPAN_CAP)
-        # occupancy is LDS-limited to ~2.5 waves/SIMD (5 blocks x 32 KiB); tell
-        # the compiler the real VGPR budget instead of spilling ~284 B/thread
-        # to scratch at a 64-VGPR default target (waves-per-SIMD tunable via
-        # TPX_MAIN_LB: 0 = no bound)
+        # the LDS staging caps occupancy at 2.5 waves/SIMD (5 blocks x 32
+        # KiB), so tell the compiler it may use the register budget of 2
+        # waves/SIMD instead of spilling ~284 B/thread to scratch at a 64-VGPR
+        # default target; large stages then take all 256 registers and run at
+        # 2 waves/SIMD (waves-per-SIMD tunable via TPX_MAIN_LB: 0 = no bound)
         import os as _os
         lb = int(_os.environ.get("TPX_MAIN_LB", "2"))
         bound = " __launch_bounds__(128, %d)" % lb if lb else ""
@@ -1565,13 +1597,24 @@ class StageCodegen:
         L.append("    long long* exc_buf, unsigned long long* exc_count,"
                  " unsigned long long exc_cap,")
         L.append("    void** outv) {")
-        L.append("  __shared__ char smem[2 * TPX_SPAN_CAP + 80];  // 2 waves per 128-thread block -> 5 blocks/CU")
+        if self.fused_window:
+            L.append("#define TPX_WCAP %d" % self.WRITE_CAP)
+            L.append("  __shared__ __attribute__((aligned(16))) char"
+                     " smem[2 * TPX_SPAN_CAP + 80 + 2 * TPX_WCAP];"
+                     "  // 40 KiB: 4 blocks/CU")
+        else:
+            L.append("  __shared__ char smem[2 * TPX_SPAN_CAP + 80];  // 2 waves per 128-thread block, 32 KiB")
         L.append("  TpxHeap heap{heap_base, heap_cursor, heap_cap, nullptr, nullptr};")
         L.append("  int lane = threadIdx.x & 63;")
         L.append("  int wid = threadIdx.x >> 6;")
         L.append("  char* wave_lds = smem + wid * TPX_SPAN_CAP;")
+        if self.fused_window:
+            L.append("  char* wave_out = smem + 2 * TPX_SPAN_CAP + 80"
+                     " + wid * TPX_WCAP;")
         L.append("  long long wave_stride = (long long)gridDim.x * (blockDim.x >> 6);")
         L.append("  long long nwaves = (n + 63) >> 6;")
+        if self.fused:
+            L.append("  const TpxCsvSink _K = *(const TpxCsvSink*)outv;")
         L.append("  for (long long wb = (long long)blockIdx.x * (blockDim.x >> 6) + wid;"
                  " wb < nwaves; wb += wave_stride) {")
         L.append("    long long r0 = wb << 6;")
@@ -1592,7 +1635,12 @@ class StageCodegen:
         L.append("      }")
         L.append("    }")
         L.append("    long long i = r0 + lane;")
-        L.append("    if (i >= rhi) continue;")
+        if self.fused:
+            # every lane stays for the wave commit; lanes past the last row
+            # take part as not-kept
+            L.append("    bool _live = i < rhi;")
+        else:
+            L.append("    if (i >= rhi) continue;")
         # Default: duplicate the row body per pointer mode — in the staged
         # branch every parse pointer provably derives from LDS, so address
         # space inference emits ds_read and no generic pointers exist. The
@@ -1885,7 +1933,79 @@ class StageCodegen:
         L.append("}")
         return "\n".join(L)
 
+    def _row_body_fused(self, in_types, out_types, lds):
+        """Row body of a fused csv-sink stage: parse + UDF chain + csv size as
+        in _row_body, but wrapped in do { } while (0) so that every early exit
+        rejoins the wave; then the wave commit (tpx_wave_commit_csv, called by
+        all 64 lanes) and the kept lanes format their row from `o` — string
+        views still pointing into LDS — straight into the wave's region of
+        the text scratch. No columnar stores, no keep/keep01/sizes."""
+        L = []
+        L.append("    Out o;")
+        L.append("    long long sz = 0;")
+        L.append("    bool _anyq = false;")
+        L.append("    bool kept = false;")
+        L.append("    do {")
+        L.append("    if (!_live) break;")
+        if self.source == "csv":
+            L.extend(self._load_inputs_csv(in_types, lds))
+        else:
+            L.extend(self._load_inputs_mem(in_types, lds))
+        args = []
+        for idx, t in enumerate(in_types):
+            args.append("c%d" % idx)
+            if T.is_opt(t):
+                args.append("c%d_n" % idx)
+        L.append("    long long rc = prc;")
+        L.append("    if (!rc) rc = tpx_process(%s, heap, o);" % ", ".join(args))
+        L.append("    if (rc != 0) {")
+        L.append("      unsigned long long e = atomicAdd(exc_count, 1ULL);")
+        L.append("      if (e < exc_cap) {")
+        L.append("        exc_buf[e*5+0] = row0 + i;")
+        L.append("        exc_buf[e*5+1] = rc & 0xFFFFFFFFLL;")
+        L.append("        exc_buf[e*5+2] = rc >> 32;")
+        L.append("        exc_buf[e*5+3] = in_offs[i];")
+        L.append("        exc_buf[e*5+4] = in_offs[i+1];")
+        L.append("      }")
+        L.append("      break;")
+        L.append("    }")
+        L.append("    if (!o.keep) break;")
+        L.extend(self._csv_size(out_types))
+        L.append("    kept = true;")
+        L.append("    } while (0);")
+        L.append("    long long _off, _tot;")
+        L.append("    char* _reg = tpx_wave_commit_csv(_K, wb, kept, sz, &_off,"
+                 " &_tot);")
+        body = self._csv_format_body(out_types, from_o=True)
+        L.append("    bool _noq = !_anyq;")
+        if self.fused_window:
+            # format into the wave's LDS output window, then move the window
+            # to the region with aligned 8-byte stores (window and region are
+            # both 8-aligned and the region is reserved in multiples of 8, so
+            # no shift and no tail). One format body per destination address
+            # space, like the row body itself. Waves above the window format
+            # directly.
+            L.append("    if (_reg && _tot <= TPX_WCAP) {")
+            L.append("      if (kept) {")
+            L.append("        char* w = wave_out + _off;")
+            L.extend("    " + ln for ln in body)
+            L.append("      }")
+            L.append("      __builtin_amdgcn_wave_barrier();")
+            L.append("      for (long long b = (long long)lane * 8; b < _tot;"
+                     " b += 64 * 8)")
+            L.append("        *(unsigned long long*)(_reg + b) ="
+                     " *(const unsigned long long*)(wave_out + b);")
+            L.append("    } else if (_reg && kept) {")
+        else:
+            L.append("    if (_reg && kept) {")
+        L.append("      char* w = _reg + _off;")
+        L.extend("  " + ln for ln in body)
+        L.append("    }")
+        return L
+
     def _row_body(self, in_types, out_types, lds):
+        if self.fused:
+            return self._row_body_fused(in_types, out_types, lds)
         L = []
         if lds == "park":
             L.extend(self._load_parsed(in_types))
@@ -2297,8 +2417,10 @@ class StageCodegen:
         \'"\' doubles. Appends newline per row. Also records whether ANY cell
         needs quoting (_anyq): the write kernel then takes a no-rescan memcpy
         fast path for the (common) fully-unquoted rows, via keep[i] bit 1."""
-        L = ["    long long sz = %d;  // delimiters + newline" % len(out_types)]
-        L.append("    bool _anyq = false;")
+        # fused sink: sz and _anyq are hoisted above the row body's wrapper
+        decl = ("", "") if self.fused else ("long long ", "bool ")
+        L = ["    %ssz = %d;  // delimiters + newline" % (decl[0], len(out_types))]
+        L.append("    %s_anyq = false;" % decl[1])
         qfree = self._thread_qfree()
         for k, t in enumerate(out_types):
             base = T.deopt(t)
@@ -2351,13 +2473,17 @@ class StageCodegen:
                     L.append("        exc_buf[e*5+3] = in_offs[i];")
                     L.append("        exc_buf[e*5+4] = in_offs[i+1];")
                 L.append("      }")
-                L.append("      keep[i] = 0; keep01[i] = 0; sizes[i] = 0;"
-                         " continue;")
+                if self.fused:
+                    L.append("      break;")
+                else:
+                    L.append("      keep[i] = 0; keep01[i] = 0; sizes[i] = 0;"
+                             " continue;")
                 L.append("    }")
                 L.append("    sz += tpx_f64_csv_len(fN%d, fg%d);" % (k, k))
             else:
                 raise CodegenError("csv sink for %r not supported yet" % (t,))
-        L.append("    sizes[i] = sz;")
+        if not self.fused:
+            L.append("    sizes[i] = sz;")
         return L
 
     def _csv_size_dup(self, store_types):
@@ -2827,7 +2953,10 @@ class StageCodegen:
         L.append("}")
         return "\n".join(L)
 
-    def _csv_format_body(self, out_types):
+    def _csv_format_body(self, out_types, from_o=False):
+        """Format one row at `w`. The write kernel reads the row's cells from
+        the columnar slots of outv; the fused main kernel (from_o) reads them
+        from its own `Out o`."""
         L = []
         for k, t in enumerate(out_types):
             base = T.deopt(t)
@@ -2836,11 +2965,17 @@ class StageCodegen:
             if base == T.STR:
                 pre = ""
                 if T.is_opt(t):
-                    L.append("    if (!((const unsigned char*)outv[%d])[i]) {"
-                             % (3 * k + 2))
+                    if from_o:
+                        L.append("    if (!o.o%d_n) {" % k)
+                    else:
+                        L.append("    if (!((const unsigned char*)outv[%d])[i]) {"
+                                 % (3 * k + 2))
                     pre = "  "
-                L.append(pre + "    tstr v%d{(const char*)((const unsigned long long*)outv[%d])[i],"
-                         " (long long)((const int*)outv[%d])[i]};" % (k, 3 * k, 3 * k + 1))
+                if from_o:
+                    L.append(pre + "    tstr v%d = o.o%d;" % (k, k))
+                else:
+                    L.append(pre + "    tstr v%d{(const char*)((const unsigned long long*)outv[%d])[i],"
+                             " (long long)((const int*)outv[%d])[i]};" % (k, 3 * k, 3 * k + 1))
                 # keep[i] bit 1 (set by the main kernel's size pass): no cell
                 # of this row needs quoting -> straight copy, no rescan
                 L.append(pre + "    if (_noq) { tpx_memcpy(w, v%d.p, v%d.n);"
@@ -2849,14 +2984,23 @@ class StageCodegen:
                 if T.is_opt(t):
                     L.append("    }")
             elif base == T.I64:
-                L.append("    { long long v = ((const long long*)outv[%d])[i];" % (3 * k))
+                if from_o:
+                    L.append("    { long long v = (long long)o.o%d;" % k)
+                else:
+                    L.append("    { long long v = ((const long long*)outv[%d])[i];" % (3 * k))
                 L.append("      long long dl = tpx_i64_digits(v); tpx_i64_write(w, v, dl); w += dl; }")
             elif base == T.BOOL:
-                L.append("    { bool v = ((const long long*)outv[%d])[i] != 0;" % (3 * k))
+                if from_o:
+                    L.append("    { bool v = o.o%d;" % k)
+                else:
+                    L.append("    { bool v = ((const long long*)outv[%d])[i] != 0;" % (3 * k))
                 L.append("      const char* s = v ? \"True\" : \"False\"; long long l = v ? 4 : 5;")
                 L.append("      for (long long j = 0; j < l; ++j) w[j] = s[j]; w += l; }")
             elif base == T.F64 and not T.is_opt(t):
-                L.append("    { double v = ((const double*)outv[%d])[i];" % (3 * k))
+                if from_o:
+                    L.append("    { double v = o.o%d;" % k)
+                else:
+                    L.append("    { double v = ((const double*)outv[%d])[i];" % (3 * k))
                 L.append("      unsigned long long fN; bool fg;")
                 L.append("      tpx_f64_csv_n(v, &fN, &fg);  // rows out of"
                          " range were diverted by the size pass")
@@ -2880,6 +3024,8 @@ class StageCodegen:
                 lines.append("agg=%s" % T.deopt(self.sp.agg_type))
         if self.csv_info.get("text_mode"):
             lines.append("textmode=1")
+        if self.fused:
+            lines.append("fusedcsv=1")
         if self.split:
             lines.append("split=1")
             if self.park_copy:

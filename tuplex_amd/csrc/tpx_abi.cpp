@@ -82,6 +82,8 @@ struct StageDesc {
     int split = 0;       // split parse/UDF kernels (csv): k_parse fills the
                          // cell park, k_main runs grid-stride over it
     int parkcopy = 0;    // 1 = dense byte park (default: zero-copy views)
+    int fusedcsv = 0;    // csv sink formatted inside k_main (no k_write):
+                         // per-batch descriptors + tpx_csv_gather
     std::vector<int> used;  // park columns (projection pushdown)
     std::vector<ColDesc> in_cols, out_cols;
 };
@@ -115,6 +117,7 @@ static bool parse_desc(const char* text, StageDesc* d) {
     d->textmode = kv.count("textmode") ? atoi(kv["textmode"].c_str()) : 0;
     d->split = kv.count("split") ? atoi(kv["split"].c_str()) : 0;
     d->parkcopy = kv.count("parkcopy") ? atoi(kv["parkcopy"].c_str()) : 0;
+    d->fusedcsv = kv.count("fusedcsv") ? atoi(kv["fusedcsv"].c_str()) : 0;
     if (kv.count("used")) {
         std::istringstream us(kv["used"]);
         std::string tok;
@@ -153,6 +156,7 @@ struct tpx_stage {
     hipFunction_t k_scan_block = nullptr, k_scan_add = nullptr;
     hipFunction_t k_pair_scan_block = nullptr, k_pair_scan_sums = nullptr;
     hipFunction_t k_pair_scan_add = nullptr;
+    hipFunction_t k_csv_gather = nullptr;
     hipFunction_t k_csv_chunk = nullptr, k_csv_sel = nullptr, k_csv_rows = nullptr;
     hipFunction_t k_red_f64 = nullptr, k_red_f64_fin = nullptr;
     hipFunction_t k_red_i64 = nullptr, k_red_i64_fin = nullptr;
@@ -259,12 +263,13 @@ extern "C" tpx_stage* tpx_stage_compile(const char* hip_source,
     struct { const char* name; hipFunction_t* fn; bool required; } lut[] = {
         {"tpx_stage_main", &st->k_main, true},
         {"tpx_stage_parse", &st->k_parse, false},
-        {"tpx_stage_write", &st->k_write, true},
+        {"tpx_stage_write", &st->k_write, !st->desc.fusedcsv},
         {"tpx_scan_block", &st->k_scan_block, true},
         {"tpx_scan_add", &st->k_scan_add, true},
         {"tpx_pair_scan_block", &st->k_pair_scan_block, true},
         {"tpx_pair_scan_sums", &st->k_pair_scan_sums, true},
         {"tpx_pair_scan_add", &st->k_pair_scan_add, true},
+        {"tpx_csv_gather", &st->k_csv_gather, st->desc.fusedcsv != 0},
         {"tpx_csv_chunk_stats", &st->k_csv_chunk, false},
         {"tpx_csv_select_counts", &st->k_csv_sel, false},
         {"tpx_csv_emit_rows", &st->k_csv_rows, false},
@@ -365,7 +370,10 @@ struct Persist {
     size_t heap_cap = 0;
     void* exc = nullptr;
     size_t exc_cap_recs = 0;
-    void* counters = nullptr;  // [cursor_c at 16*c (c<4) ... exc_count at 80]
+    void* counters = nullptr;  // [heap cursor_c at 16*c, text cursor_c at
+                               //  16*c+8 (c<8) ... exc_count at 128]
+    void* text = nullptr;      // fused csv sink: text scratch, split per chunk
+    size_t text_cap = 0;
 };
 static Persist g_persist[64];
 
@@ -507,24 +515,42 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     hipEvent_t evm0 = EP.get(), evs1 = EP.get();
     hipEventRecord(ev1, stream);
 
+    // fused csv sink (desc fusedcsv=1): k_main formats kept rows into a text
+    // scratch and leaves one descriptor per 64-row batch; a pair scan over
+    // the descriptors and tpx_csv_gather replace the per-row compaction scans
+    // and k_write. No columnar slots, keep/keep01/sizes or per-row scans.
+    const bool fused = D.fusedcsv != 0;
+    if (fused && (!st->k_csv_gather || !d_offs)) {
+        set_err("fused csv sink: gather kernel or row offsets missing");
+        return -1;
+    }
+
     // output columnar buffers (3 slots per column) from the arena
     int nout = (int)D.out_cols.size();
     std::vector<void*> outv((size_t)nout * 3, nullptr);
-    for (int k = 0; k < nout; ++k)
-        for (int s = 0; s < 3; ++s) {
-            size_t b = col_slot_bytes(D.out_cols[(size_t)k], n, s);
-            if (b) {
-                outv[(size_t)k * 3 + s] = g_arena[dev].take(b);
-                if (!outv[(size_t)k * 3 + s]) return -1;
+    void* d_outv = nullptr;
+    void* d_keep = nullptr;
+    void* d_keep01 = nullptr;
+    void* d_sizes = nullptr;
+    if (!fused) {
+        for (int k = 0; k < nout; ++k)
+            for (int s = 0; s < 3; ++s) {
+                size_t b = col_slot_bytes(D.out_cols[(size_t)k], n, s);
+                if (b) {
+                    outv[(size_t)k * 3 + s] = g_arena[dev].take(b);
+                    if (!outv[(size_t)k * 3 + s]) return -1;
+                }
             }
-        }
-    ARENA_TAKE(d_outv, outv.size() * sizeof(void*) + 8);
-    HIP_CHECK(hipMemcpyAsync(d_outv, outv.data(), outv.size() * sizeof(void*),
-                             hipMemcpyHostToDevice, stream));
-
-    ARENA_TAKE(d_keep, (size_t)n);
-    ARENA_TAKE(d_keep01, (size_t)n * 8);
-    ARENA_TAKE(d_sizes, (size_t)n * 8);
+        d_outv = g_arena[dev].take(outv.size() * sizeof(void*) + 8);
+        if (!d_outv) return -1;
+        HIP_CHECK(hipMemcpyAsync(d_outv, outv.data(),
+                                 outv.size() * sizeof(void*),
+                                 hipMemcpyHostToDevice, stream));
+        d_keep = g_arena[dev].take((size_t)n);
+        d_keep01 = g_arena[dev].take((size_t)n * 8);
+        d_sizes = g_arena[dev].take((size_t)n * 8);
+        if (!d_keep || !d_keep01 || !d_sizes) return -1;
+    }
 
     // persistent heap / exception buffer / counters
     if (!P.counters)
@@ -598,7 +624,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     // per-chunk biased outv pointer tables (chunk rows index columnar slot i
     // locally); chunk 0 table == the unbiased one
     void* d_outv_c[8] = {d_outv};
-    if (C > 1) {
+    if (C > 1 && !fused) {
         std::vector<void*> ovall(outv.size() * (size_t)(C - 1));
         for (int c = 1; c < C; ++c) {
             void** ov = ovall.data() + outv.size() * (size_t)(c - 1);
@@ -719,6 +745,29 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     }
     heap_cap = P.heap_cap;
 
+    // fused csv sink: persistent text scratch, grown and never shrunk like
+    // the heap and split per chunk like it. Initial capacity: half the input
+    // bytes (Zillow Z1 writes 0.15 output bytes per input byte) plus the
+    // 8-byte rounding of every batch's region. TPX_TEXT_CAP0 (bytes, read
+    // once) caps every execute's FIRST attempt, so a test can force the
+    // overflow retry.
+    static long long env_text_cap0 = [] {
+        const char* e = getenv("TPX_TEXT_CAP0");
+        return e ? atoll(e) : -1LL;
+    }();
+    if (fused) {
+        size_t want = (size_t)(in_bytes / 2) + (size_t)(n / 64 + 1) * 8 +
+                      ((size_t)1 << 20);
+        if (env_text_cap0 >= 0) want = (size_t)env_text_cap0 + 64;
+        if (P.text_cap < want) {
+            if (P.text) (void)hipFree(P.text);
+            P.text = nullptr;
+            P.text_cap = 0;
+            HIP_CHECK(hipMalloc(&P.text, want + 16));  // word-read pad
+            P.text_cap = want;
+        }
+    }
+
     void* d_exc_count = (char*)P.counters + 128;
     unsigned long long exc_count = 0;
     // per chunk [main end = scans start, totals ready, write start, write end]
@@ -734,17 +783,57 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     void* d_out_offs = nullptr;
     void* d_out_rowidx = nullptr;
     bool sink_done = false;
+    unsigned long long ts = 0;  // fused csv sink: text scratch bytes per chunk
+    // fused csv sink, per chunk: b_off, b_rows, b_bytes, rows scan, bytes
+    // scan, rmeta
+    void* fb[8][6] = {};
     for (int attempt = 0;; ++attempt) {
         HIP_CHECK(hipMemsetAsync(P.counters, 0, 160, stream));
         hipEventRecord(evm0, stream);
         unsigned long long hs = heap_cap / (unsigned long long)C & ~255ull;
-        if (C > 1) {
+        if (C > 1 && !fused) {
             d_out_offs = g_arena[dev].take(((size_t)n + 1) * 8);
             d_out_rowidx = g_arena[dev].take(((size_t)n + 1) * 8);
             d_keep_scan = g_arena[dev].take((size_t)n * 8);
             d_size_scan = g_arena[dev].take((size_t)n * 8);
             if (!d_out_offs || !d_out_rowidx || !d_keep_scan || !d_size_scan)
                 return -1;
+        }
+        if (fused) {
+            // per chunk: b_off / b_rows / b_bytes and the two scans, one
+            // entry per 64-row batch; rmeta, one record per row slot; and the
+            // seven-slot table that k_main gets in place of outv
+            unsigned long long tcap =
+                (attempt == 0 && env_text_cap0 >= 0)
+                    ? (unsigned long long)env_text_cap0 : P.text_cap;
+            ts = tcap / (unsigned long long)C & ~7ull;
+            d_out_offs = g_arena[dev].take(((size_t)n + 1) * 8);
+            d_out_rowidx = g_arena[dev].take(((size_t)n + 1) * 8);
+            if (!d_out_offs || !d_out_rowidx) return -1;
+            void* tab[8][7] = {};
+            for (int c = 0; c < C; ++c) {
+                size_t nbc = (size_t)((ccnt[c] + 63) / 64);
+                for (int k = 0; k < 5; ++k) {
+                    fb[c][k] = g_arena[dev].take(nbc * 8);
+                    if (!fb[c][k]) return -1;
+                }
+                fb[c][5] = g_arena[dev].take(nbc * 64 * 8);
+                if (!fb[c][5]) return -1;
+                tab[c][0] = (char*)P.text + (unsigned long long)c * ts;
+                tab[c][1] = (char*)P.counters + 16 * c + 8;
+                tab[c][2] = (void*)(uintptr_t)ts;
+                tab[c][3] = fb[c][0];
+                tab[c][4] = fb[c][1];
+                tab[c][5] = fb[c][2];
+                tab[c][6] = fb[c][5];
+            }
+            void* blk = g_arena[dev].take(sizeof tab);
+            if (!blk) return -1;
+            HIP_CHECK(hipMemcpyAsync(blk, tab, sizeof tab,
+                                     hipMemcpyHostToDevice, stream));
+            for (int c = 0; c < C; ++c)
+                d_outv_c[c] = (char*)blk + sizeof(tab[0]) * (size_t)c;
+            hipEventRecord(evm0, stream);  // the side streams wait for the table
         }
         for (int c = 0; c < C; ++c) {
             hipStream_t sc = S[c & 1];
@@ -753,7 +842,8 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                 (*pre_chunk)(cstart[c], cstart[c + 1], sc))
                 return -1;
             // main runs 128-thread blocks (2 waves x 16 KiB LDS staging =
-            // 32 KiB -> 5 blocks/CU = 10 waves/CU); each wave owns 64 rows
+            // 32 KiB -> at most 5 blocks/CU; 4 where the stage takes all 256
+            // registers per lane); each wave owns 64 rows
             long long nc = ccnt[c];
             long long waves = (nc + 63) / 64;
             unsigned grid = (unsigned)std::min<long long>((waves + 1) / 2, 4096);
@@ -762,9 +852,9 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
             long long row0_c = row0 + cstart[c];
             void* heap_c = (char*)P.heap + (unsigned long long)c * hs;
             void* cursor_c = (char*)P.counters + 16 * c;
-            void* keep_c = (char*)d_keep + cstart[c];
-            void* keep01_c = (char*)d_keep01 + cstart[c] * 8;
-            void* sizes_c = (char*)d_sizes + cstart[c] * 8;
+            void* keep_c = fused ? nullptr : (char*)d_keep + cstart[c];
+            void* keep01_c = fused ? nullptr : (char*)d_keep01 + cstart[c] * 8;
+            void* sizes_c = fused ? nullptr : (char*)d_sizes + cstart[c] * 8;
             if (split) {
                 if (attempt == 0) {  // park is attempt-invariant
                     void* prc_c = (char*)d_prc + cstart[c] * 8;
@@ -788,27 +878,36 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                 if (launch(st->k_main, grid, 128, sc, args)) return -1;
             }
             hipEventRecord(cev[(size_t)c * 4], sc);
-            if (C > 1) {
+            if (C > 1 || fused) {
                 // chunk c's compaction, in stream order right behind main c:
-                // fused pair scan of (keep01, sizes), then both totals into
-                // the chunk's own pinned slot; the host picks them up below
-                // without blocking this stream (main c+2 queues behind)
+                // fused pair scan of (keep01, sizes) — for the fused csv sink
+                // of the per-batch (rows, bytes) descriptors, 1/64 as many —
+                // then both totals into the chunk's own pinned slot; the host
+                // picks them up below without blocking this stream (main c+2
+                // queues behind)
                 const long long BLOCK = 2048;  // TPX_SCAN_BLOCK
-                long long nblocks = (nc + BLOCK - 1) / BLOCK;
-                void* kscan_c = (char*)d_keep_scan + cstart[c] * 8;
-                void* sscan_c = (char*)d_size_scan + cstart[c] * 8;
+                long long nscan = fused ? (nc + 63) / 64 : nc;
+                long long nblocks = (nscan + BLOCK - 1) / BLOCK;
+                void* kscan_c = fused ? fb[c][3]
+                                      : (char*)d_keep_scan + cstart[c] * 8;
+                void* sscan_c = fused ? fb[c][4]
+                                      : (char*)d_size_scan + cstart[c] * 8;
+                if (fused) {
+                    keep01_c = fb[c][1];
+                    sizes_c = fb[c][2];
+                }
                 void* sums = g_arena[dev].take((size_t)nblocks * 16);
                 void* offs = g_arena[dev].take((size_t)nblocks * 16);
                 void* slot = g_arena[dev].take(16);
                 if (!sums || !offs || !slot) return -1;
                 void* a1[] = {&keep01_c, &sizes_c, &kscan_c, &sscan_c, &sums,
-                              &nc};
+                              &nscan};
                 if (nblocks > 0 && launch(st->k_pair_scan_block,
                                           (unsigned)nblocks, 256, sc, a1))
                     return -1;
                 void* a2[] = {&sums, &nblocks, &offs, &slot};
                 if (launch(st->k_pair_scan_sums, 1, 256, sc, a2)) return -1;
-                void* a3[] = {&kscan_c, &sscan_c, &offs, &nc};
+                void* a3[] = {&kscan_c, &sscan_c, &offs, &nscan};
                 if (nblocks > 1 && launch(st->k_pair_scan_add,
                                           (unsigned)nblocks, 256, sc, a3))
                     return -1;
@@ -822,8 +921,11 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         // keep=false, so the write reads no garbage; on the rare overflow the
         // attempt is simply redone). The host waits on each chunk's totals
         // EVENT — not its stream, later mains are queued there — and launches
-        // the write on the write stream.
-        if (C > 1) {
+        // the write on the write stream. The fused csv sink takes this path
+        // for C == 1 too (every stream is `stream` then): its gather is
+        // optimistic in the same way, since a wave whose text did not fit
+        // left an empty descriptor.
+        if (C > 1 || fused) {
             total_rows = total_bytes = 0;
             const long long hdr = mem_sink ? 8 : 0;
             for (int c = 0; c < C; ++c) {
@@ -862,7 +964,21 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                                 &rows_c, &bytes_c, &out_byte0};
                 hipStreamWaitEvent(SW, cev[(size_t)c * 4 + 1], 0);
                 hipEventRecord(cev[(size_t)c * 4 + 2], SW);
-                if (launch(st->k_write, grid, 128, SW, args)) return -1;
+                if (fused) {
+                    // one wave per batch, 4 waves per 256-thread block
+                    long long nbc = (ccnt[c] + 63) / 64;
+                    unsigned gg = (unsigned)std::min<long long>(
+                        (nbc + 3) / 4, 8192);
+                    if (gg < 1) gg = 1;
+                    void* text_c = (char*)P.text + (unsigned long long)c * ts;
+                    void* ga[] = {&text_c, &fb[c][0], &fb[c][1], &fb[c][2],
+                                  &fb[c][3], &fb[c][4], &fb[c][5], &nbc,
+                                  &row0_c, &chunk_out[c], &offs_c, &ridx_c,
+                                  &out_byte0};
+                    if (launch(st->k_csv_gather, gg, 256, SW, ga)) return -1;
+                } else if (launch(st->k_write, grid, 128, SW, args)) {
+                    return -1;
+                }
                 hipEventRecord(cev[(size_t)c * 4 + 3], SW);
                 chunk_bytes[c] = bytes_c;
                 total_rows += rows_c;
@@ -896,12 +1012,17 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         exc_count = counters[16];
         bool heap_overflow = max_used > hs;
         bool exc_overflow = exc_count > exc_cap;
-        if (!heap_overflow && !exc_overflow) {
-            sink_done = C > 1;
+        unsigned long long text_used = 0;
+        if (fused)
+            for (int c = 0; c < C; ++c)
+                text_used = std::max(text_used, counters[c * 2 + 1]);
+        bool text_overflow = text_used > ts;
+        if (!heap_overflow && !exc_overflow && !text_overflow) {
+            sink_done = C > 1 || fused;
             break;
         }
         if (attempt >= 3) { set_err("retry limit (heap/exc overflow)"); return -1; }
-        if (C > 1) {
+        if (C > 1 || fused) {
             // the optimistic writes and gather copies of this attempt still
             // use the buffers the next attempt rewrites (and may free)
             HIP_CHECK(hipStreamSynchronize(S[0]));
@@ -916,6 +1037,19 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                        (unsigned long long)C;
             HIP_CHECK(hipMalloc(&P.heap, heap_cap + 16));
             P.heap_cap = heap_cap;
+        }
+        if (text_overflow) {
+            // grow to the cursors' high-water mark plus half (waves that did
+            // not fit advanced their cursor all the same); never truncate
+            size_t want = (size_t)(text_used + (text_used >> 1) + 4096) *
+                          (size_t)C;
+            if (P.text_cap < want) {
+                (void)hipFree(P.text);
+                P.text = nullptr;
+                P.text_cap = 0;
+                HIP_CHECK(hipMalloc(&P.text, want + 16));
+                P.text_cap = want;
+            }
         }
         if (exc_overflow) {
             (void)hipFree(P.exc);

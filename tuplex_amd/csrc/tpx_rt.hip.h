@@ -1022,6 +1022,60 @@ __device__ __forceinline__ long long tpx_wave_sum(long long v) {
     return __shfl((long long)v, 0);
 }
 
+// Fused csv sink: tpx_stage_main formats kept rows itself. The table its
+// `outv` argument points to then holds, per chunk, these seven slots instead
+// of columnar output arrays.
+struct TpxCsvSink {
+    char* text;                  // chunk's text scratch (8-aligned)
+    unsigned long long* cursor;  // bytes reserved so far (may pass cap)
+    unsigned long long cap;      // capacity of `text`
+    long long* b_off;            // per 64-row batch: region offset in `text`
+    long long* b_rows;           // per batch: kept rows
+    long long* b_bytes;          // per batch: text bytes
+    unsigned long long* rmeta;   // 64 per batch: lane << 32 | offset in batch
+};
+
+// Wave commit of one 64-row batch `wb`: every lane of the wave calls it with
+// its row's `kept` flag and csv size `sz` (lanes past the last row: not kept).
+// Lane 0 reserves the wave's region, rounded up to 8 bytes so every region
+// starts 8-aligned, with ONE atomicAdd, and stores the batch descriptor; kept
+// lanes store their rmeta record at their rank among the kept lanes. Returns
+// the wave's region (the same pointer in every lane), *off = this lane's byte
+// offset inside it and *tot = the wave's text bytes; or nullptr for a wave
+// that writes nothing. A wave whose region would end past the capacity
+// writes no text and an empty descriptor; the cursor still advances, so the
+// host sees the overflow and redoes the attempt with a larger scratch.
+__device__ __forceinline__ char* tpx_wave_commit_csv(const TpxCsvSink& K,
+                                                     long long wb, bool kept,
+                                                     long long sz,
+                                                     long long* off_out,
+                                                     long long* tot_out) {
+    int lane = threadIdx.x & 63;
+    long long v = kept ? sz : 0;
+    long long off = tpx_wave_exscan(v);
+    long long tot = tpx_wave_sum(v);
+    unsigned long long m = __ballot(kept);
+    int rank = __popcll(m & ((1ull << lane) - 1ull));
+    unsigned long long base = 0;
+    if (lane == 0) {
+        unsigned long long need = ((unsigned long long)tot + 7ull) & ~7ull;
+        if (need) base = atomicAdd(K.cursor, need);
+        bool fits = base + need <= K.cap;
+        K.b_off[wb] = fits ? (long long)base : 0;
+        K.b_rows[wb] = fits ? (long long)__popcll(m) : 0;
+        K.b_bytes[wb] = fits ? tot : 0;
+        if (!fits) base = ~0ull;
+    }
+    base = __shfl((unsigned long long)base, 0);
+    *off_out = off;
+    *tot_out = tot;
+    if (base == ~0ull || tot == 0) return nullptr;
+    if (kept)
+        K.rmeta[wb * 64 + rank] =
+            ((unsigned long long)lane << 32) | (unsigned long long)off;
+    return K.text + base;
+}
+
 // per-lane scan of its 64-byte slice: counts quotes and newlines at even/odd
 // LOCAL quote parity. Coalesced uint4 loads when the slice is full.
 __device__ __forceinline__ void tpx_scan64(const char* __restrict__ data,
@@ -1963,6 +2017,57 @@ extern "C" __global__ void tpx_pair_scan_add(long long* __restrict__ a_out,
             a_out[i] += adda;
             b_out[i] += addb;
         }
+    }
+}
+
+// Fused csv sink, second step: one wave per 64-row batch (grid-stride) moves
+// the batch's text from its region of the scratch to its final place and
+// writes the row offsets and row indices of its kept rows. rows_scan and
+// bytes_scan are the exclusive pair scan of (b_rows, b_bytes). Regions start
+// 8-aligned and are reserved in multiples of 8, so the copy reads whole
+// aligned words and stores aligned 8-byte words through a funnel shift that
+// is uniform across the wave, with byte stores for the unaligned head and
+// tail; it writes no byte outside [bytes_before, bytes_before + bytes).
+extern "C" __global__ void tpx_csv_gather(
+    const char* __restrict__ text, const long long* __restrict__ b_off,
+    const long long* __restrict__ b_rows, const long long* __restrict__ b_bytes,
+    const long long* __restrict__ rows_scan,
+    const long long* __restrict__ bytes_scan,
+    const unsigned long long* __restrict__ rmeta, long long nb, long long row0,
+    char* __restrict__ out, long long* __restrict__ out_offs,
+    long long* __restrict__ out_rowidx, long long out_byte0) {
+    int lane = threadIdx.x & 63;
+    long long wave_stride = (long long)gridDim.x * (blockDim.x >> 6);
+    for (long long wb = (long long)blockIdx.x * (blockDim.x >> 6) +
+                        (threadIdx.x >> 6);
+         wb < nb; wb += wave_stride) {
+        long long rows = b_rows[wb];
+        long long bytes = b_bytes[wb];
+        long long rows_before = rows_scan[wb];
+        long long bytes_before = bytes_scan[wb];
+        if (lane < rows) {
+            unsigned long long m = rmeta[wb * 64 + lane];
+            out_offs[rows_before + lane] =
+                out_byte0 + bytes_before + (long long)(m & 0xFFFFFFFFull);
+            out_rowidx[rows_before + lane] =
+                row0 + wb * 64 + (long long)(m >> 32);
+        }
+        const char* src = text + b_off[wb];
+        const unsigned long long* sw = (const unsigned long long*)src;
+        char* dst = out + bytes_before;
+        long long a0 = (8 - (long long)((unsigned long long)dst & 7)) & 7;
+        if (lane < a0 && lane < bytes) dst[lane] = src[lane];
+        int sh = (int)a0 * 8;
+        for (long long b = a0 + (long long)lane * 8; b + 8 <= bytes;
+             b += 64 * 8) {
+            long long w = (b - a0) >> 3;
+            unsigned long long lo = sw[w];
+            unsigned long long v = lo;
+            if (sh) v = (lo >> sh) | (sw[w + 1] << (64 - sh));
+            *(unsigned long long*)(dst + b) = v;
+        }
+        long long t0 = bytes > a0 ? a0 + ((bytes - a0) & ~7LL) : bytes;
+        if (t0 + lane < bytes) dst[t0 + lane] = src[t0 + lane];
     }
 }
 #endif  // TPX_HOST_TEST
