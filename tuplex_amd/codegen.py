@@ -64,6 +64,18 @@ def fmt_header() -> str:
     return _FMT_HEADER_CACHE
 
 
+_CI_HEADER_CACHE = None
+
+
+def ci_header() -> str:
+    global _CI_HEADER_CACHE
+    if _CI_HEADER_CACHE is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                            "csrc", "tpx_ci.hip.h")
+        _CI_HEADER_CACHE = open(path).read()
+    return _CI_HEADER_CACHE
+
+
 def _ctype(t):
     base = T.deopt(t)
     if base in (T.I64,):
@@ -1493,6 +1505,24 @@ class StageCodegen:
         # for 5 blocks of 32 KiB gives one up.
         self.fused_window = (self.fused and
                              _os.environ.get("TPX_FUSED_WINDOW", "1") != "0")
+        # Wave-cooperative cell index (csrc/tpx_ci.hip.h): the staging loop
+        # classifies the span's bytes while it holds them in registers and
+        # leaves one LDS entry per structural byte; a lane takes its row's
+        # cells from the entries and walks the row itself (tpx_mw_cell) only
+        # if tpx_ci_row declines it. Only for LDS-staged csv stages with a
+        # ',' delimiter (with another delimiter a comma marks a cell for
+        # output quoting, which block-granular bitmaps cannot resolve), not
+        # text mode, and at most CI_MAX_COLS columns; every other stage keeps
+        # its source byte for byte. TPX_CELL_INDEX, like TPX_FUSED_SINK, is
+        # read here, at codegen time.
+        self.cell_index = (
+            self.source == "csv" and not self.split
+            and not self.csv_info.get("text_mode")
+            and self.csv_info.get("delimiter", ",") == ","
+            and 1 <= len(in_types) <= self.CI_MAX_COLS
+            and _os.environ.get("TPX_GEN_BODY") != "1"
+            and _os.environ.get("TPX_CELL_INDEX",
+                                self.CELL_INDEX_DEFAULT) != "0")
         if self.split:
             main_src = ("#define TPX_SPAN_CAP %d\n" % self.SPAN_CAP +
                         self._parse_kernel(in_types) + "\n\n" +
@@ -1511,7 +1541,8 @@ class StageCodegen:
             "// generated by tuplex_amd.codegen — stage %s" % sp.signature(),
             runtime_header(),
             "",
-        ] + self._re_section() + self._fmt_section() + self.lit_defs + \
+        ] + self._ci_section() + self._re_section() + self._fmt_section() + \
+            self.lit_defs + \
             self.join_defs + [
             "",
             "struct Out {",
@@ -1537,6 +1568,16 @@ class StageCodegen:
         if not getattr(self, "re_defs", None):
             return []
         return [regex_header(), ""] + self.re_defs
+
+    def _ci_section(self):
+        """Cell-index header — only for stages that take the index path
+        (same reasoning as _re_section)."""
+        if not self.cell_index:
+            return []
+        return [ci_header(),
+                "static_assert(64 * %d + 1 <= TPX_CI_CAP,"
+                " \"a full batch of well-formed rows fits the index\");"
+                % len(self.sp.input_types), ""]
 
     def _fmt_section(self):
         """String-builder header + embedded templates — only for stages with a
@@ -1569,9 +1610,22 @@ class StageCodegen:
     # tighter limit: its code object allocates 256 registers per lane
     # (.vgpr_count 256: 128 VGPRs plus 128 that hold spills), i.e. 2
     # waves/SIMD = 8 waves/CU = 4 blocks (profiles/README.md, round 4). Small
-    # stages stay LDS-limited at 5 blocks. The 80-B tail absorbs the mask
+    # stages stay LDS-limited at 5 blocks, unless they carry the output
+    # window or the cell index region (40 KiB: 4 blocks; see CI_BYTES
+    # below). The 80-B tail absorbs the mask
     # walk's aligned 64-B group overread past the last row of a wave's span.
     SPAN_CAP = 16344
+    # Cell-index region per wave: tpx_ci.hip.h's layout in CI_BYTES. A batch
+    # of 64 well-formed rows of c columns has 64*c entries (+1 virtual
+    # terminator), so the widest stage that can never overflow the list has
+    # (CI_CAP - 1) // 64 columns. For fused-window stages the region IS the
+    # wave's output window (idle until after tpx_wave_commit_csv, and every
+    # index read precedes the commit in program order); other stages get a
+    # region of their own. Either way the block is 40 960 B: 4 blocks/CU.
+    CI_BYTES = 4096
+    CI_CAP = (CI_BYTES - 264) // 4
+    CI_MAX_COLS = (CI_CAP - 1) // 64
+    CELL_INDEX_DEFAULT = "1"
 
     def _main_kernel(self, in_types, out_types):
         if self.source == "col":
@@ -1602,6 +1656,10 @@ class StageCodegen:
             L.append("  __shared__ __attribute__((aligned(16))) char"
                      " smem[2 * TPX_SPAN_CAP + 80 + 2 * TPX_WCAP];"
                      "  // 40 KiB: 4 blocks/CU")
+        elif self.cell_index:
+            L.append("  __shared__ __attribute__((aligned(16))) char"
+                     " smem[2 * TPX_SPAN_CAP + 80 + 2 * TPX_CI_BYTES];"
+                     "  // 40 KiB: 4 blocks/CU")
         else:
             L.append("  __shared__ char smem[2 * TPX_SPAN_CAP + 80];  // 2 waves per 128-thread block, 32 KiB")
         L.append("  TpxHeap heap{heap_base, heap_cursor, heap_cap, nullptr, nullptr};")
@@ -1611,6 +1669,14 @@ class StageCodegen:
         if self.fused_window:
             L.append("  char* wave_out = smem + 2 * TPX_SPAN_CAP + 80"
                      " + wid * TPX_WCAP;")
+        if self.cell_index:
+            if self.fused_window:
+                assert self.WRITE_CAP == self.CI_BYTES
+                L.append("  char* wave_ci = wave_out;  // idle until the"
+                         " wave commit")
+            else:
+                L.append("  char* wave_ci = smem + 2 * TPX_SPAN_CAP + 80"
+                         " + wid * TPX_CI_BYTES;")
         L.append("  long long wave_stride = (long long)gridDim.x * (blockDim.x >> 6);")
         L.append("  long long nwaves = (n + 63) >> 6;")
         if self.fused:
@@ -1625,15 +1691,24 @@ class StageCodegen:
         # NB: never form (wave_lds - span_start): an LDS generic pointer offset
         # outside the aperture is UB once the addrspace-inference pass narrows it
         L.append("    bool staged = span <= TPX_SPAN_CAP;")
-        L.append("    if (staged) {")
-        L.append("      for (long long k = (long long)lane * 16; k < span; k += 64 * 16) {")
-        L.append("        if (k + 16 <= span)")
-        L.append("          *(uint4*)(wave_lds + k) = *(const uint4*)((const char*)in_data + span_start + k);")
-        L.append("        else")
-        L.append("          for (long long j = k; j < span; ++j)")
-        L.append("            wave_lds[j] = ((const char*)in_data)[span_start + j];")
-        L.append("      }")
-        L.append("    }")
+        if self.cell_index:
+            # staging + index in one pass, all 64 lanes, before any lane
+            # leaves for `_live` / `continue`
+            L.append("    bool _ci_ok = false;")
+            L.append("    if (staged)")
+            L.append("      _ci_ok = tpx_ci_stage(wave_lds, wave_ci,"
+                     " (const char*)in_data + span_start, (int)span,"
+                     " (int)(in_offs[r0] - span_start), ',', lane);")
+        else:
+            L.append("    if (staged) {")
+            L.append("      for (long long k = (long long)lane * 16; k < span; k += 64 * 16) {")
+            L.append("        if (k + 16 <= span)")
+            L.append("          *(uint4*)(wave_lds + k) = *(const uint4*)((const char*)in_data + span_start + k);")
+            L.append("        else")
+            L.append("          for (long long j = k; j < span; ++j)")
+            L.append("            wave_lds[j] = ((const char*)in_data)[span_start + j];")
+            L.append("      }")
+            L.append("    }")
         L.append("    long long i = r0 + lane;")
         if self.fused:
             # every lane stays for the wave commit; lanes past the last row
@@ -2207,6 +2282,16 @@ class StageCodegen:
         L.append("    tpx_mwalk S; tpx_mw_init(S, rp, rend);")
         L.append("    bool avail = true;")
         L.append("    int badf = 0;")
+        # cell index (staged body only): an accepted row reads its cells
+        # from the wave's entry list, cell bounds at first use; a declined
+        # row is walked from its start exactly as without the index
+        ci = self.cell_index and lds is True
+        if ci:
+            L.append("    int _rs = (int)(in_offs[i] - span_start);")
+            L.append("    int _e0 = 0;")
+            L.append("    bool _fast = _ci_ok && tpx_ci_row(wave_lds, wave_ci,"
+                     " lane, _rs, (int)(in_offs[i+1] - span_start),"
+                     " (int)(rend - wave_lds), (int)span, %d, &_e0);" % nc)
 
         def null_check(idx):
             cv = "tstr{cl%d.p, cl%d.n}" % (idx, idx)
@@ -2223,7 +2308,14 @@ class StageCodegen:
             opt = T.is_opt(t)
             L.append("    tpx_cell cl%d{rp, 0, 0};" % idx)
             L.append("    if (!prc) {")
-            L.append("      if (!avail) prc = %d;  // CSV_UNDERRUN" % 20)
+            if ci:
+                L.append("      if (_fast) tpx_ci_cell(wave_lds, wave_ci, _e0,"
+                         " %d, %d, _rs, (int)(rend - wave_lds), &cl%d);"
+                         % (idx, nc, idx))
+                L.append("      else if (!avail) prc = %d;  // CSV_UNDERRUN"
+                         % 20)
+            else:
+                L.append("      if (!avail) prc = %d;  // CSV_UNDERRUN" % 20)
             L.append("      else { tpx_mw_cell(S, &cl%d, %s, %d);"
                      " avail = S.more; badf |= cl%d.flags; }"
                      % (idx, delim_c, chk_comma, idx))
@@ -2263,6 +2355,9 @@ class StageCodegen:
                          % (guard, idx, idx, 70))
             else:
                 raise CodegenError("csv input type %r" % (t,))
+        if ci:
+            # accepted: exactly nc cells, flags 0 or 1|8, no byte >= 0x80
+            L.append("    if (_fast) avail = false;")
         L.append("    if (!prc && avail) prc = %d;  // CSV_OVERRUN" % 21)
         L.append("    if (!prc && (badf & 6)) prc = %d;  // BADPARSE (escapes/structure -> host)" % 70)
         # ONE ASCII gate per row, fused into the group-mask loads (rows that
