@@ -1508,7 +1508,8 @@ class StageCodegen:
         # Wave-cooperative cell index (csrc/tpx_ci.hip.h): the staging loop
         # classifies the span's bytes while it holds them in registers and
         # leaves one LDS entry per structural byte; a lane takes its row's
-        # cells from the entries and walks the row itself (tpx_mw_cell) only
+        # cells from the entries and walks the row itself (tpx_mw_cell, in one
+        # out-of-line tpx_walk_row call unless TPX_OUTLINE=0) only
         # if tpx_ci_row declines it. Only for LDS-staged csv stages with a
         # ',' delimiter (with another delimiter a comma marks a cell for
         # output quoting, which block-granular bitmaps cannot resolve), not
@@ -1523,6 +1524,15 @@ class StageCodegen:
             and _os.environ.get("TPX_GEN_BODY") != "1"
             and _os.environ.get("TPX_CELL_INDEX",
                                 self.CELL_INDEX_DEFAULT) != "0")
+        # Cold paths out of line (TPX_COLD in csrc/tpx_rt.hip.h, and below:
+        # the unstaged batch, the walk of a declined row, the direct format
+        # of a wave above the window). TPX_OUTLINE=0, read here like
+        # TPX_CELL_INDEX, emits everything inline for A/B runs in one tree;
+        # TPX_OUTLINE=2 also de-inlines the helpers a UDF chain calls many
+        # times (measured slower: round 6 of profiles/README.md).
+        self.outline_level = 2 if _os.environ.get("TPX_OUTLINE") == "2" else 1
+        self.outline = (_os.environ.get("TPX_OUTLINE", "1") != "0"
+                        and _os.environ.get("TPX_GEN_BODY") != "1")
         if self.split:
             main_src = ("#define TPX_SPAN_CAP %d\n" % self.SPAN_CAP +
                         self._parse_kernel(in_types) + "\n\n" +
@@ -1539,6 +1549,8 @@ class StageCodegen:
             write_src = self._write_kernel_csv_dup(out_types, store_types)
         src = [
             "// generated by tuplex_amd.codegen — stage %s" % sp.signature(),
+        ] + (["#define TPX_OUTLINE %d" % self.outline_level]
+             if self.outline else []) + [
             runtime_header(),
             "",
         ] + self._ci_section() + self._re_section() + self._fmt_section() + \
@@ -1607,9 +1619,10 @@ class StageCodegen:
     # bytes per wave: 2 waves/block stage 2*CAP+80 B of LDS; 16344 keeps the
     # block at exactly 32768 B, so by LDS alone FIVE blocks fit the 160 KiB CU
     # budget (10 waves/CU). For a stage as large as Zillow Z1 registers are the
-    # tighter limit: its code object allocates 256 registers per lane
-    # (.vgpr_count 256: 128 VGPRs plus 128 that hold spills), i.e. 2
-    # waves/SIMD = 8 waves/CU = 4 blocks (profiles/README.md, round 4). Small
+    # tighter limit: its staged row body alone needs 225 registers per lane,
+    # and the code object allocates 248 with the out-of-line unstaged batch
+    # (256 with 275 spills before the cold paths moved out of line), i.e. 2
+    # waves/SIMD = 8 waves/CU = 4 blocks (profiles/README.md, rounds 4, 6). Small
     # stages stay LDS-limited at 5 blocks, unless they carry the output
     # window or the cell index region (40 KiB: 4 blocks; see CI_BYTES
     # below). The 80-B tail absorbs the mask
@@ -1640,19 +1653,29 @@ class StageCodegen:
         import os as _os
         lb = int(_os.environ.get("TPX_MAIN_LB", "2"))
         bound = " __launch_bounds__(128, %d)" % lb if lb else ""
+        params = [
+            "    const unsigned char* __restrict__ in_data,",
+            "    const long long* __restrict__ in_offs,",
+            "    long long n, long long row0,",
+            "    char* heap_base, unsigned long long* heap_cursor,"
+            " unsigned long long heap_cap,",
+            "    unsigned char* __restrict__ keep, long long* __restrict__ keep01,",
+            "    long long* __restrict__ sizes,",
+            "    long long* exc_buf, unsigned long long* exc_count,"
+            " unsigned long long exc_cap,",
+            "    void** outv"]
+        if self.outline:
+            if self.fused_window:
+                # ahead of the out-of-line unstaged batch, which formats
+                # into the window too
+                L.append("#define TPX_WCAP %d" % self.WRITE_CAP)
+            L.extend(self._outlined_bodies(in_types, out_types, params))
         L.append('extern "C" __global__ void%s tpx_stage_main(' % bound)
-        L.append("    const unsigned char* __restrict__ in_data,")
-        L.append("    const long long* __restrict__ in_offs,")
-        L.append("    long long n, long long row0,")
-        L.append("    char* heap_base, unsigned long long* heap_cursor,"
-                 " unsigned long long heap_cap,")
-        L.append("    unsigned char* __restrict__ keep, long long* __restrict__ keep01,")
-        L.append("    long long* __restrict__ sizes,")
-        L.append("    long long* exc_buf, unsigned long long* exc_count,"
-                 " unsigned long long exc_cap,")
-        L.append("    void** outv) {")
+        L.extend(params[:-1])
+        L.append(params[-1] + ") {")
         if self.fused_window:
-            L.append("#define TPX_WCAP %d" % self.WRITE_CAP)
+            if not self.outline:
+                L.append("#define TPX_WCAP %d" % self.WRITE_CAP)
             L.append("  __shared__ __attribute__((aligned(16))) char"
                      " smem[2 * TPX_SPAN_CAP + 80 + 2 * TPX_WCAP];"
                      "  // 40 KiB: 4 blocks/CU")
@@ -1718,7 +1741,9 @@ class StageCodegen:
             L.append("    if (i >= rhi) continue;")
         # Default: duplicate the row body per pointer mode — in the staged
         # branch every parse pointer provably derives from LDS, so address
-        # space inference emits ds_read and no generic pointers exist. The
+        # space inference emits ds_read and no generic pointers exist (the
+        # unstaged copy is the out-of-line tpx_batch_unstaged unless
+        # TPX_OUTLINE=0 keeps it here as the else arm). The
         # single generic-pointer body (TPX_GEN_BODY=1) halves kernel size and
         # hipRTC compile time but MISCOMPILES on hipRTC gfx950 (mem-path null
         # VAs survived three opaque-pointer workarounds; see commits
@@ -1729,13 +1754,77 @@ class StageCodegen:
             L.append("    if (staged) {")
             L.extend("  " + ln
                      for ln in self._row_body(in_types, out_types, lds=True))
-            L.append("    } else {")
-            L.extend("  " + ln
-                     for ln in self._row_body(in_types, out_types, lds=False))
-            L.append("    }")
+            if self.outline:
+                L.append("    }")
+            else:
+                L.append("    } else {")
+                L.extend("  " + ln for ln in
+                         self._row_body(in_types, out_types, lds=False))
+                L.append("    }")
         L.append("  }")
+        if self.outline:
+            # The wave's unstaged batches, in a loop of their own after the
+            # batch loop: a call of tpx_batch_unstaged INSIDE the batch loop
+            # made everything that lives through the loop compete for the
+            # callee-saved registers and cost the staged arm 148 VGPR spills
+            # (Zillow Z1); here next to nothing is live across the call.
+            # Batches are independent (region, descriptor and row slots are
+            # keyed by batch and row), so their order within a wave is free.
+            L.append("  for (long long wb = (long long)blockIdx.x *"
+                     " (blockDim.x >> 6) + wid; wb < nwaves;"
+                     " wb += wave_stride) {")
+            L.append("    long long r0 = wb << 6;")
+            L.append("    long long rhi = r0 + 64 < n ? r0 + 64 : n;")
+            L.append("    if (in_offs[rhi] - (in_offs[r0] & ~15LL)"
+                     " <= TPX_SPAN_CAP) continue;  // wave-uniform")
+            L.append("    tpx_batch_unstaged(in_data, in_offs, n, row0,"
+                     " heap_base, heap_cursor, heap_cap, keep, keep01,"
+                     " sizes, exc_buf, exc_count, exc_cap, outv, lane,"
+                     " wb, r0, rhi%s);"
+                     % (", wave_out" if self.fused_window else ""))
+            L.append("  }")
         L.append("}")
         return "\n".join(L)
+
+    def _outlined_bodies(self, in_types, out_types, params):
+        """Device functions tpx_stage_main calls instead of carrying their
+        code: the row body of a batch whose span exceeds TPX_SPAN_CAP (parse
+        from global memory, UDF chain, commit, format: the whole `!staged`
+        arm, so the kernel's registers are sized by the staged arm alone),
+        and for fused-window stages the format of one row straight to global
+        memory, for waves whose text exceeds the window."""
+        L = []
+        if self.fused_window:
+            L.append("__device__ __attribute__((noinline)) void"
+                     " tpx_format_row_direct(char* w, const Out o,"
+                     " bool _noq) {")
+            L.extend(self._csv_format_body(out_types, from_o=True))
+            L.append("}")
+            L.append("")
+        L.append("__device__ __attribute__((noinline)) void"
+                 " tpx_batch_unstaged(")
+        L.extend(params[:-1])
+        L.append(params[-1] + ", int lane, long long wb, long long r0,"
+                 " long long rhi%s) {"
+                 % (", char* wave_out" if self.fused_window else ""))
+        # a heap view of its own: the per-thread chunk of the kernel's view
+        # stays in the kernel's registers, a reference to it would not
+        L.append("  TpxHeap heap{heap_base, heap_cursor, heap_cap, nullptr,"
+                 " nullptr};")
+        if self.fused:
+            L.append("  const TpxCsvSink _K = *(const TpxCsvSink*)outv;")
+        L.append("  long long i = r0 + lane;")
+        if self.fused:
+            L.append("  bool _live = i < rhi;")
+        else:
+            L.append("  if (i >= rhi) return;")
+        # the row body leaves a row with `continue`, as in the batch loop
+        L.append("  do {")
+        L.extend(self._row_body(in_types, out_types, lds=False))
+        L.append("  } while (0);")
+        L.append("}")
+        L.append("")
+        return L
 
     # -- split parse/UDF kernels (csv source) --------------------------------
     # tpx_stage_parse: the LDS-staged cell walk + typed parse, writing a dense
@@ -2063,7 +2152,17 @@ class StageCodegen:
             L.append("    if (_reg && _tot <= TPX_WCAP) {")
             L.append("      if (kept) {")
             L.append("        char* w = wave_out + _off;")
-            L.extend("    " + ln for ln in body)
+            if self.outline:
+                # inline: the row no cell of which needs quoting, a length
+                # and a copy per cell. A row with a cell to quote goes to
+                # the out-of-line row formatter in ONE call, `o` by value,
+                # so that nothing of `o` has to live across a call.
+                L.append("        if (_noq) {")
+                L.extend("      " + ln for ln in self._csv_format_body(
+                    out_types, from_o=True, noq_only=True))
+                L.append("        } else tpx_format_row_direct(w, o, false);")
+            else:
+                L.extend("    " + ln for ln in body)
             L.append("      }")
             L.append("      __builtin_amdgcn_wave_barrier();")
             L.append("      for (long long b = (long long)lane * 8; b < _tot;"
@@ -2071,6 +2170,12 @@ class StageCodegen:
             L.append("        *(unsigned long long*)(_reg + b) ="
                      " *(const unsigned long long*)(wave_out + b);")
             L.append("    } else if (_reg && kept) {")
+            if self.outline:
+                # rare (the wave's text exceeds the window): one shared
+                # out-of-line copy; `o` goes by value
+                L.append("      tpx_format_row_direct(_reg + _off, o, _noq);")
+                L.append("    }")
+                return L
         else:
             L.append("    if (_reg && kept) {")
         L.append("      char* w = _reg + _off;")
@@ -2279,9 +2384,22 @@ class StageCodegen:
         # ALU bit derivation; the ASCII gate and output-special (quote
         # provenance) tracking ride along for free.
         chk_comma = 1 if delim != "," else 0
-        L.append("    tpx_mwalk S; tpx_mw_init(S, rp, rend);")
-        L.append("    bool avail = true;")
-        L.append("    int badf = 0;")
+        # Index stages with the cold paths out of line: a row is walked by
+        # ONE call of tpx_walk_row, all cells at once, and only if the index
+        # declined it (staged body) or there is no index (unstaged body);
+        # an accepted row builds no walk state at all. Walking ahead of the
+        # typed parses changes nothing: the walk has no side effects, and
+        # column k still reports UNDERRUN only if no earlier column failed.
+        wf = self.outline and self.cell_index and lds in (True, False)
+        if wf:
+            L.append("    bool avail = true;")
+            L.append("    int badf = 0;")
+            L.append("    bool _hib = false;")
+            L.append("    int _nw = %d;  // cells the walk produced" % nc)
+        else:
+            L.append("    tpx_mwalk S; tpx_mw_init(S, rp, rend);")
+            L.append("    bool avail = true;")
+            L.append("    int badf = 0;")
         # cell index (staged body only): an accepted row reads its cells
         # from the wave's entry list, cell bounds at first use; a declined
         # row is walked from its start exactly as without the index
@@ -2303,23 +2421,49 @@ class StageCodegen:
         # + column-count errors keep reference semantics) but their typed
         # parse / null check is skipped (plan._used_source_columns)
         used = getattr(self.sp, "used_source_cols", None)
+        if wf:
+            for idx in range(nc):
+                L.append("    tpx_cell cl%d{rp, 0, 0};" % idx)
+            L.append("    if (!_fast) {" if ci else "    {")
+            L.append("      tpx_rowcells<%d> _W = tpx_walk_row<%d, %s, %d>"
+                     "(rp, rend);" % (nc, nc, delim_c, chk_comma))
+            for idx in range(nc):
+                L.append("      cl%d = tpx_cell{rp + _W.off[%d], _W.n[%d],"
+                         " (int)((_W.flags >> %d) & 15)};"
+                         % (idx, idx, idx, 4 * idx))
+            L.append("      _nw = _W.ncells; avail = _W.more;"
+                     " badf = _W.badf; _hib = _W.hib;")
+            L.append("    }")
         for idx, t in enumerate(in_types):
             base = T.deopt(t)
             opt = T.is_opt(t)
-            L.append("    tpx_cell cl%d{rp, 0, 0};" % idx)
-            L.append("    if (!prc) {")
-            if ci:
-                L.append("      if (_fast) tpx_ci_cell(wave_lds, wave_ci, _e0,"
-                         " %d, %d, _rs, (int)(rend - wave_lds), &cl%d);"
-                         % (idx, nc, idx))
-                L.append("      else if (!avail) prc = %d;  // CSV_UNDERRUN"
-                         % 20)
+            if wf:
+                L.append("    if (!prc) {")
+                if ci:
+                    L.append("      if (_fast) tpx_ci_cell(wave_lds, wave_ci,"
+                             " _e0, %d, %d, _rs, (int)(rend - wave_lds),"
+                             " &cl%d);" % (idx, nc, idx))
+                    L.append("      else if (%d >= _nw) prc = %d;"
+                             "  // CSV_UNDERRUN" % (idx, 20))
+                else:
+                    L.append("      if (%d >= _nw) prc = %d;"
+                             "  // CSV_UNDERRUN" % (idx, 20))
+                L.append("    }")
             else:
-                L.append("      if (!avail) prc = %d;  // CSV_UNDERRUN" % 20)
-            L.append("      else { tpx_mw_cell(S, &cl%d, %s, %d);"
-                     " avail = S.more; badf |= cl%d.flags; }"
-                     % (idx, delim_c, chk_comma, idx))
-            L.append("    }")
+                L.append("    tpx_cell cl%d{rp, 0, 0};" % idx)
+                L.append("    if (!prc) {")
+                if ci:
+                    L.append("      if (_fast) tpx_ci_cell(wave_lds, wave_ci, _e0,"
+                             " %d, %d, _rs, (int)(rend - wave_lds), &cl%d);"
+                             % (idx, nc, idx))
+                    L.append("      else if (!avail) prc = %d;  // CSV_UNDERRUN"
+                             % 20)
+                else:
+                    L.append("      if (!avail) prc = %d;  // CSV_UNDERRUN" % 20)
+                L.append("      else { tpx_mw_cell(S, &cl%d, %s, %d);"
+                         " avail = S.more; badf |= cl%d.flags; }"
+                         % (idx, delim_c, chk_comma, idx))
+                L.append("    }")
             if used is not None and idx not in used:
                 if opt:
                     L.append("    bool c%d_n = false;  // unused (pushdown)" % idx)
@@ -2363,7 +2507,8 @@ class StageCodegen:
         # ONE ASCII gate per row, fused into the group-mask loads (rows that
         # error out earlier divert regardless, so partial accumulation over
         # the loaded groups is equivalent)
-        L.append("    if (!prc && S.hib) prc = %d;  // NCV" % 7)
+        L.append("    if (!prc && %s) prc = %d;  // NCV"
+                 % ("_hib" if wf else "S.hib", 7))
         return L
 
     def _load_inputs_text(self, in_types, lds=True):
@@ -3048,10 +3193,11 @@ class StageCodegen:
         L.append("}")
         return "\n".join(L)
 
-    def _csv_format_body(self, out_types, from_o=False):
+    def _csv_format_body(self, out_types, from_o=False, noq_only=False):
         """Format one row at `w`. The write kernel reads the row's cells from
         the columnar slots of outv; the fused main kernel (from_o) reads them
-        from its own `Out o`."""
+        from its own `Out o`. noq_only: the body of a row known to need no
+        quoting (string cells are copied, tpx_csv_cell_write is not named)."""
         L = []
         for k, t in enumerate(out_types):
             base = T.deopt(t)
@@ -3073,9 +3219,14 @@ class StageCodegen:
                              " (long long)((const int*)outv[%d])[i]};" % (k, 3 * k, 3 * k + 1))
                 # keep[i] bit 1 (set by the main kernel's size pass): no cell
                 # of this row needs quoting -> straight copy, no rescan
-                L.append(pre + "    if (_noq) { tpx_memcpy(w, v%d.p, v%d.n);"
-                         " w += v%d.n; }" % (k, k, k))
-                L.append(pre + "    else w = tpx_csv_cell_write(w, v%d);" % k)
+                if noq_only:
+                    L.append(pre + "    tpx_memcpy(w, v%d.p, v%d.n);"
+                             " w += v%d.n;" % (k, k, k))
+                else:
+                    L.append(pre + "    if (_noq) { tpx_memcpy(w, v%d.p,"
+                             " v%d.n); w += v%d.n; }" % (k, k, k))
+                    L.append(pre + "    else w = tpx_csv_cell_write(w, v%d);"
+                             % k)
                 if T.is_opt(t):
                     L.append("    }")
             elif base == T.I64:

@@ -22,6 +22,32 @@
 
 #define TPX_WAVE 64
 
+// TPX_OUTLINE (defined by codegen ahead of this header; TPX_OUTLINE=0 in the
+// environment at codegen time leaves it out). Level 1, the default: code a
+// well-formed batch does not execute is real functions (TPX_COLD) instead of
+// inlined copies. Level 2, for measurements only: so are the helpers a UDF
+// chain instantiates many times (TPX_SHARED) — each call on the hot path
+// costs the caller spills of what is live across it (Zillow Z1: 24 VGPRs),
+// see profiles/README.md, round 6. Either kind takes and returns values
+// only: a pointer to a caller's local would pin that local to scratch.
+// Without the switch both are __forceinline__ and every stage compiles to
+// what it was.
+#ifndef TPX_OUTLINE
+#define TPX_OUTLINE 0
+#endif
+#if TPX_OUTLINE
+#define TPX_COLD __attribute__((noinline))
+#else
+#define TPX_COLD __forceinline__
+#endif
+#if TPX_OUTLINE >= 2
+#define TPX_SHARED __attribute__((noinline))
+#else
+#define TPX_SHARED __forceinline__
+#endif
+struct tpx_i64r { long long v; int ec; };
+struct tpx_f64r { double v; int ec; };
+
 // ExceptionCodes.h:26 values (subset used on device)
 #define EC_OK 0
 #define EC_NCV 7            // NORMALCASEVIOLATION -> silent host replay
@@ -411,7 +437,7 @@ __device__ __forceinline__ long long tpx_find(const tstr s, const tstr needle, i
     return -1;
 }
 
-__device__ __forceinline__ long long tpx_rfind(const tstr s, const tstr needle, int* ec) {
+__device__ TPX_SHARED long long tpx_rfind_v(const tstr s, const tstr needle) {
     if (needle.n == 0) return s.n;
     long long hi = s.n - needle.n;  // highest candidate start
     while (hi >= 0) {
@@ -424,6 +450,10 @@ __device__ __forceinline__ long long tpx_rfind(const tstr s, const tstr needle, 
         hi = k - 1;
     }
     return -1;
+}
+
+__device__ __forceinline__ long long tpx_rfind(const tstr s, const tstr needle, int* ec) {
+    return tpx_rfind_v(s, needle);
 }
 
 __device__ __forceinline__ bool tpx_contains(const tstr s, const tstr needle) {
@@ -575,6 +605,39 @@ __device__ __forceinline__ tstr tpx_capitalize_ix(TpxHeap& h, const tstr s, int*
 __device__ __forceinline__ tstr tpx_replace(TpxHeap& h, const tstr s, const tstr a,
                                             const tstr b, int* ec);
 __device__ __forceinline__ long long tpx_int_str(const tstr s, int* ec);
+#if TPX_OUTLINE >= 2
+// Out of line the long tail allocates from a heap view of its own (the
+// cursor is shared, the per-thread chunk is not): the copy it makes is
+// dead once parsed, so only the chunk's remainder is given up.
+__device__ TPX_SHARED tpx_i64r tpx_int_drop_v(char* hbase, unsigned long long* hcur,
+                                            unsigned long long hcap, const tstr s,
+                                            char drop, const tstr drop_s) {
+    tpx_i64r r{0, 0};
+    if (s.n <= 31) {
+        char buf[32];
+        long long m = 0;
+        for (long long i = 0; i < s.n; ++i) {
+            char c = s.p[i];
+            if (c != drop) buf[m++] = c;
+        }
+        r.v = tpx_int_str(tstr{buf, m}, &r.ec);
+        return r;
+    }
+    TpxHeap h{hbase, hcur, hcap, nullptr, nullptr};
+    tstr t = tpx_replace(h, s, drop_s, tstr{s.p, 0}, &r.ec);
+    if (r.ec) return r;
+    r.v = tpx_int_str(t, &r.ec);
+    return r;
+}
+
+__device__ __forceinline__ long long tpx_int_drop(TpxHeap& h, const tstr s,
+                                                  char drop, const tstr drop_s,
+                                                  int* ec) {
+    tpx_i64r r = tpx_int_drop_v(h.base, h.cursor, h.cap, s, drop, drop_s);
+    if (r.ec) *ec = r.ec;
+    return r.v;
+}
+#else
 __device__ __forceinline__ long long tpx_int_drop(TpxHeap& h, const tstr s,
                                                   char drop, const tstr drop_s,
                                                   int* ec) {
@@ -591,6 +654,7 @@ __device__ __forceinline__ long long tpx_int_drop(TpxHeap& h, const tstr s,
     if (*ec) return 0;
     return tpx_int_str(r, ec);
 }
+#endif
 
 __device__ __forceinline__ tstr tpx_swapcase(TpxHeap& h, const tstr s, int* ec) {
     char* d = tpx_alloc(h, s.n);
@@ -768,26 +832,37 @@ __device__ __forceinline__ int tpx_fast_atod(const char* start, const char* end,
 
 // Runtime.cc:319 wrappers: trim python whitespace both ends, then parse;
 // parse error -> VALUEERROR
-__device__ __forceinline__ long long tpx_int_str(const tstr s, int* ec) {
-    const char* a = s.p;
-    const char* b = s.p + s.n;
+// trim + parse by value: {value (0 unless parsed), fast_atoX's code}
+__device__ TPX_SHARED tpx_i64r tpx_trim_atoi64(const char* p, long long n) {
+    const char* a = p;
+    const char* b = p + n;
     while (a < b && tpx_is_pyws(*a)) ++a;
     while (b > a && tpx_is_pyws(*(b - 1))) --b;
-    long long v = 0;
-    int r = tpx_fast_atoi64(a, b, &v);
-    if (r != EC_OK) *ec = EC_VALUEERROR;
-    return v;
+    tpx_i64r r{0, 0};
+    r.ec = tpx_fast_atoi64(a, b, &r.v);
+    return r;
+}
+
+__device__ TPX_SHARED tpx_f64r tpx_trim_atod(const char* p, long long n) {
+    const char* a = p;
+    const char* b = p + n;
+    while (a < b && tpx_is_pyws(*a)) ++a;
+    while (b > a && tpx_is_pyws(*(b - 1))) --b;
+    tpx_f64r r{0.0, 0};
+    r.ec = tpx_fast_atod(a, b, &r.v);
+    return r;
+}
+
+__device__ __forceinline__ long long tpx_int_str(const tstr s, int* ec) {
+    tpx_i64r r = tpx_trim_atoi64(s.p, s.n);
+    if (r.ec != EC_OK) *ec = EC_VALUEERROR;
+    return r.v;
 }
 
 __device__ __forceinline__ double tpx_float_str(const tstr s, int* ec) {
-    const char* a = s.p;
-    const char* b = s.p + s.n;
-    while (a < b && tpx_is_pyws(*a)) ++a;
-    while (b > a && tpx_is_pyws(*(b - 1))) --b;
-    double v = 0.0;
-    int r = tpx_fast_atod(a, b, &v);
-    if (r != EC_OK) *ec = EC_VALUEERROR;
-    return v;
+    tpx_f64r r = tpx_trim_atod(s.p, s.n);
+    if (r.ec != EC_OK) *ec = EC_VALUEERROR;
+    return r.v;
 }
 
 // int(float): python truncates toward zero; OverflowError outside i64
@@ -852,7 +927,8 @@ __device__ __forceinline__ tstr tpx_str_none() { return tstr{"None", 4}; }
 // SWAR: 8 bytes per step (called twice per output string — size pass in the
 // main kernel, then the write kernel — so the byte loop was ~2x70B of serial
 // dependent loads per kept row). Head/tail stay byte-wise: no over-read.
-__device__ __forceinline__ bool tpx_csv_needs_quote(const tstr s, long long* nquotes) {
+// by value: the number of '"' in s, or -1 if s needs no quoting
+__device__ TPX_SHARED long long tpx_csv_quote_scan(const tstr s) {
     bool need = false;
     long long q = 0;
     long long i = 0;
@@ -904,8 +980,13 @@ __device__ __forceinline__ bool tpx_csv_needs_quote(const tstr s, long long* nqu
         if (c == '"') { ++q; need = true; }
         else if (c == ',' || c == '\n' || c == '\r') need = true;
     }
-    *nquotes = q;
-    return need;
+    return need ? q : -1;
+}
+
+__device__ __forceinline__ bool tpx_csv_needs_quote(const tstr s, long long* nquotes) {
+    long long q = tpx_csv_quote_scan(s);
+    *nquotes = q < 0 ? 0 : q;
+    return q >= 0;
 }
 
 __device__ __forceinline__ long long tpx_csv_cell_len(const tstr s) {
@@ -913,7 +994,8 @@ __device__ __forceinline__ long long tpx_csv_cell_len(const tstr s) {
     return tpx_csv_needs_quote(s, &q) ? s.n + q + 2 : s.n;
 }
 
-__device__ __forceinline__ char* tpx_csv_cell_write(char* w, const tstr s) {
+// only rows with a cell to quote come here (keep bit 1 / _noq clear)
+__device__ TPX_COLD char* tpx_csv_cell_write(char* w, const tstr s) {
     long long q;
     if (tpx_csv_needs_quote(s, &q)) {
         *w++ = '"';
@@ -938,8 +1020,10 @@ __device__ __forceinline__ char* tpx_csv_cell_write(char* w, const tstr s) {
 // inf divert the row (NCV-style: the host formatter produces the identical
 // text on replay). -------------------------------------------------------------
 
-__device__ __forceinline__ int tpx_f64_csv_n(double v, unsigned long long* N,
-                                             bool* neg) {
+struct tpx_f64n { unsigned long long N; int rc; bool neg; };
+
+__device__ __forceinline__ int tpx_f64_csv_n_(double v, unsigned long long* N,
+                                              bool* neg) {
     unsigned long long bits = (unsigned long long)__double_as_longlong(v);
     *neg = (bits >> 63) != 0;
     int exp = (int)((bits >> 52) & 0x7FF);
@@ -969,6 +1053,21 @@ __device__ __forceinline__ int tpx_f64_csv_n(double v, unsigned long long* N,
     return 0;
 }
 
+__device__ TPX_SHARED tpx_f64n tpx_f64_csv_n_v(double v) {
+    tpx_f64n r{0, 0, false};
+    r.rc = tpx_f64_csv_n_(v, &r.N, &r.neg);
+    return r;
+}
+
+// *N is written only where the value fits (rc 0), as before
+__device__ __forceinline__ int tpx_f64_csv_n(double v, unsigned long long* N,
+                                             bool* neg) {
+    tpx_f64n r = tpx_f64_csv_n_v(v);
+    if (r.rc == 0) *N = r.N;
+    *neg = r.neg;
+    return r.rc;
+}
+
 __device__ __forceinline__ long long tpx_f64_csv_len(unsigned long long N,
                                                      bool neg) {
     int d = 1;
@@ -978,9 +1077,9 @@ __device__ __forceinline__ long long tpx_f64_csv_len(unsigned long long N,
     return (neg ? 1 : 0) + d + 1;
 }
 
-__device__ __forceinline__ char* tpx_f64_csv_write(char* w,
-                                                   unsigned long long N,
-                                                   bool neg) {
+__device__ TPX_SHARED char* tpx_f64_csv_write(char* w,
+                                            unsigned long long N,
+                                            bool neg) {
     char buf[21];
     int nd = 0;
     unsigned long long t = N;
@@ -1501,22 +1600,66 @@ __device__ __forceinline__ void tpx_mw_cell(tpx_mwalk& S, tpx_cell* c,
     if (nd < S.endb) { S.more = true; S.pos = nd + 1; } else S.pos = S.endb;
 }
 
+// All cells of one row by the mask walk, as one call: what a row that the
+// cell index declined (and every row of an unstaged batch) costs the kernel
+// is this call, not NC inlined walks. By value, as offsets from rp: cell k is
+// {rp + off[k], n[k], (flags >> 4k) & 15} for k < ncells, the walk having
+// stopped where no delimiter followed; `more` = a delimiter followed cell
+// NC-1 (overrun); badf = OR of the cells' flags; hib = a byte >= 0x80 in the
+// groups the walk loaded. The loop is not unrolled: one copy of the walk.
+template <int NC>
+struct tpx_rowcells {
+    int off[NC];
+    int n[NC];
+    unsigned long long flags;
+    int ncells;
+    int badf;
+    bool more;
+    bool hib;
+};
+
+template <int NC, char DELIM, int CHK>
+__device__ TPX_COLD tpx_rowcells<NC> tpx_walk_row(const char* rp,
+                                                  const char* rend) {
+    static_assert(NC <= 16, "4 flag bits per cell in 64");
+    tpx_rowcells<NC> R;
+    tpx_mwalk S;
+    tpx_mw_init(S, rp, rend);
+    R.flags = 0;
+    R.ncells = 0;
+    R.badf = 0;
+    bool avail = true;
+    #pragma unroll 1
+    for (int k = 0; k < NC; ++k) {
+        R.off[k] = 0;
+        R.n[k] = 0;
+        if (!avail) continue;
+        tpx_cell c;
+        tpx_mw_cell(S, &c, DELIM, CHK);
+        avail = S.more;
+        R.off[k] = (int)(c.p - rp);
+        R.n[k] = (int)c.n;
+        R.flags |= (unsigned long long)(c.flags & 15) << (4 * k);
+        R.badf |= c.flags;
+        R.ncells = k + 1;
+    }
+    R.more = avail;
+    R.hib = S.hib != 0;
+    return R;
+}
+
 // typed cell parse (cells path semantics: python-whitespace trim + fast_atoX,
 // CellSourceTaskBuilder + Runtime.cc:319 wrappers)
 __device__ __forceinline__ int tpx_cell_i64(const tpx_cell& c, long long* out) {
-    const char* a = c.p;
-    const char* b = c.p + c.n;
-    while (a < b && tpx_is_pyws(*a)) ++a;
-    while (b > a && tpx_is_pyws(*(b - 1))) --b;
-    return tpx_fast_atoi64(a, b, out);
+    tpx_i64r r = tpx_trim_atoi64(c.p, c.n);
+    if (r.ec == EC_OK) *out = r.v;
+    return r.ec;
 }
 
 __device__ __forceinline__ int tpx_cell_f64(const tpx_cell& c, double* out) {
-    const char* a = c.p;
-    const char* b = c.p + c.n;
-    while (a < b && tpx_is_pyws(*a)) ++a;
-    while (b > a && tpx_is_pyws(*(b - 1))) --b;
-    return tpx_fast_atod(a, b, out);
+    tpx_f64r r = tpx_trim_atod(c.p, c.n);
+    if (r.ec == EC_OK) *out = r.v;
+    return r.ec;
 }
 
 // fast_atob semantics (StringUtils.cc:186): case-insensitive
