@@ -30,20 +30,6 @@
 #define TPX_CI_CAP ((TPX_CI_BYTES - TPX_CI_ENT_OFF) / 4)
 #define TPX_CI_NONE 0xFFFFu
 
-// exact, borrow-free zero-byte detect on a dword (see tpx_swar_zero)
-__device__ __forceinline__ unsigned tpx_ci_zero32(unsigned x) {
-    return ~(x | ((x | 0x80808080u) - 0x01010101u)) & 0x80808080u;
-}
-
-// the four 0x80-position bits of a dword -> bits 0..3 (byte j -> bit j);
-// shifts only: bits {0,8,16,24} -> {0,1,16,17,..} -> {0,1,2,3,..}
-__device__ __forceinline__ unsigned tpx_ci_pack4(unsigned h) {
-    unsigned x = h >> 7;
-    x |= x >> 7;
-    x |= x >> 14;
-    return x & 0xFu;
-}
-
 // 16-bit positional class masks of a lane's 16 bytes (bit j = byte j), cut to
 // `valid`: q '"', s delimiter or '\n', n '\n', r '\r', h byte >= 0x80
 struct tpx_ci_cls { unsigned q, s, n, r, h; };
@@ -60,25 +46,21 @@ __device__ __forceinline__ void tpx_ci_classify(unsigned w0, unsigned w1,
     #pragma unroll
     for (int d = 0; d < 4; ++d) {
         unsigned v = w[d];
-        unsigned zn = tpx_ci_zero32(v ^ pn);
-        q |= tpx_ci_pack4(tpx_ci_zero32(v ^ pq)) << (4 * d);
-        s |= tpx_ci_pack4(tpx_ci_zero32(v ^ pd) | zn) << (4 * d);
-        n |= tpx_ci_pack4(zn) << (4 * d);
-        r |= tpx_ci_pack4(tpx_ci_zero32(v ^ pr)) << (4 * d);
-        h |= tpx_ci_pack4(v & 0x80808080u) << (4 * d);
+        unsigned zn = tpx_bs_zero32(v ^ pn);
+        q |= tpx_bs_pack4(tpx_bs_zero32(v ^ pq)) << (4 * d);
+        s |= tpx_bs_pack4(tpx_bs_zero32(v ^ pd) | zn) << (4 * d);
+        n |= tpx_bs_pack4(zn) << (4 * d);
+        r |= tpx_bs_pack4(tpx_bs_zero32(v ^ pr)) << (4 * d);
+        h |= tpx_bs_pack4(v & 0x80808080u) << (4 * d);
     }
     c->q = q & valid; c->s = s & valid; c->n = n & valid;
     c->r = r & valid; c->h = h & valid;
 }
 
-// bit j = byte j lies inside quotes: parity of the '"' bytes before it, `par`
-// being the parity of all '"' bytes before the lane's byte 0
+// the in-lane quote state is tpx_bs_inq of tpx_rt.hip.h, which the boundary
+// kernels share; the index keeps its own name for it
 __device__ __forceinline__ unsigned tpx_ci_inq(unsigned q16, unsigned par) {
-    unsigned x = q16;
-    x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8;  // inclusive prefix xor
-    x <<= 1;                                              // exclusive
-    if (par) x = ~x;
-    return x & 0xFFFFu;
+    return tpx_bs_inq(q16, par);
 }
 
 // one lane's structural bytes -> entries ord0.. in position order; an
@@ -205,15 +187,6 @@ __device__ __forceinline__ void tpx_ci_cell(const char* base, const char* ci,
 }
 
 #ifndef TPX_HOST_TEST  // device-only: the wave glue of the index builder
-__device__ __forceinline__ unsigned tpx_wave_exscan32(unsigned v, int lane) {
-    unsigned x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        unsigned y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    return x - v;  // exclusive
-}
-
 // Stage span bytes [0, span) of the wave's batch from global memory into
 // wave_lds, as the plain staging loop does, and build the cell index of the
 // bytes from `lo` (the first row's start; the span start is rounded down to

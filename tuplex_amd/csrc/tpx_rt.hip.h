@@ -1103,7 +1103,106 @@ __device__ TPX_SHARED char* tpx_f64_csv_write(char* w,
 // parallel-exact restatement of the reference's sequential state machine.
 
 #define TPX_CSV_CHUNK 4096
-#define TPX_CSV_LANE_BYTES 64  /* 4096 / 64 lanes */
+
+// ---- per-lane pieces of the boundary kernels (and of the cell index) ------------
+// Plain C, no wave intrinsics: tests/host_boundary_test.cpp runs them on the
+// host. A lane handles a 16-byte piece as four little-endian dwords.
+
+// exact, borrow-free zero-byte detect on a dword (see tpx_swar_zero)
+__device__ __forceinline__ unsigned tpx_bs_zero32(unsigned x) {
+    return ~(x | ((x | 0x80808080u) - 0x01010101u)) & 0x80808080u;
+}
+
+// the four 0x80-position bits of a dword -> bits 0..3 (byte j -> bit j);
+// shifts only: bits {0,8,16,24} -> {0,1,16,17,..} -> {0,1,2,3,..}
+__device__ __forceinline__ unsigned tpx_bs_pack4(unsigned h) {
+    unsigned x = h >> 7;
+    x |= x >> 7;
+    x |= x >> 14;
+    return x & 0xFu;
+}
+
+// bit j = byte j lies inside quotes: parity of the '"' bytes before it, `par`
+// being the parity of all '"' bytes before the lane's byte 0
+__device__ __forceinline__ unsigned tpx_bs_inq(unsigned q16, unsigned par) {
+    unsigned x = q16;
+    x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8;  // inclusive prefix xor
+    x <<= 1;                                              // exclusive
+    if (par) x = ~x;
+    return x & 0xFFFFu;
+}
+
+// detect words of a piece: q[d] / n[d] flag the '"' / '\n' bytes of dword d at
+// their 0x80 bits; mq / mn hold all four words' flags at distinct bits (dword d
+// at bit 7-d of each byte), so popc(mq) is the piece's quote count and mq == 0
+// means it has none. quotes_on == 0: the quote class is empty.
+struct tpx_bs_det { unsigned q[4], n[4], mq, mn; };
+
+__device__ __forceinline__ void tpx_bs_detect(unsigned w0, unsigned w1,
+                                              unsigned w2, unsigned w3,
+                                              int quotes_on, tpx_bs_det* d) {
+    const unsigned pq = 0x01010101u * (unsigned)'"';
+    const unsigned pn = 0x01010101u * (unsigned)'\n';
+    unsigned w[4] = {w0, w1, w2, w3};
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        d->n[i] = tpx_bs_zero32(w[i] ^ pn);
+        d->q[i] = quotes_on ? tpx_bs_zero32(w[i] ^ pq) : 0u;
+    }
+    d->mn = d->n[0] | d->n[1] >> 1 | d->n[2] >> 2 | d->n[3] >> 3;
+    d->mq = d->q[0] | d->q[1] >> 1 | d->q[2] >> 2 | d->q[3] >> 3;
+}
+
+// four detect words -> positional 16-bit mask (bit j = byte j of the piece)
+__device__ __forceinline__ unsigned tpx_bs_pos16(const unsigned h[4]) {
+    return tpx_bs_pack4(h[0]) | tpx_bs_pack4(h[1]) << 4 |
+           tpx_bs_pack4(h[2]) << 8 | tpx_bs_pack4(h[3]) << 12;
+}
+
+// chunk_stats' view of a piece: *nq '"' bytes, *e / *o newlines after an even /
+// odd number of the piece's OWN quotes. A piece without a quote is all at one
+// parity and needs no positions; only one with both classes builds the masks.
+// (__builtin_popcount: the host programs of tests/ compile this too.)
+__device__ __forceinline__ void tpx_bs_count16(unsigned w0, unsigned w1,
+                                               unsigned w2, unsigned w3,
+                                               int quotes_on, unsigned* nq,
+                                               unsigned* e, unsigned* o) {
+    tpx_bs_det d;
+    tpx_bs_detect(w0, w1, w2, w3, quotes_on, &d);
+    unsigned nn = (unsigned)__builtin_popcount(d.mn), od = 0;
+    if (d.mq && d.mn)
+        od = (unsigned)__builtin_popcount(tpx_bs_pos16(d.n) &
+                              tpx_bs_inq(tpx_bs_pos16(d.q), 0u));
+    *nq = (unsigned)__builtin_popcount(d.mq);
+    *e = nn - od;
+    *o = od;
+}
+
+// emit_rows' view: the positional mask of the piece's newlines outside quotes,
+// `par` being the parity of every '"' byte before the piece
+__device__ __forceinline__ unsigned tpx_bs_rows16(const tpx_bs_det* d,
+                                                  unsigned par) {
+    if (!d->mn) return 0u;
+    unsigned n16 = tpx_bs_pos16(d->n);
+    if (!d->mq) return par ? 0u : n16;
+    return n16 & ~tpx_bs_inq(tpx_bs_pos16(d->q), par);
+}
+
+// a piece that is not wholly inside the input: bytes [k, size) of it by a byte
+// loop, the rest zero (a zero byte is in neither class), nothing read at or
+// after `size`
+__device__ __forceinline__ void tpx_bs_load_tail(const char* data, long long k,
+                                                 long long size, unsigned w[4]) {
+    unsigned long long a = 0, b = 0;
+    for (long long j = k; j < size && j < k + 16; ++j) {
+        unsigned long long ch = (unsigned char)data[j];
+        int t = (int)(j - k);
+        if (t < 8) a |= ch << (8 * t);
+        else b |= ch << (8 * (t - 8));
+    }
+    w[0] = (unsigned)a; w[1] = (unsigned)(a >> 32);
+    w[2] = (unsigned)b; w[3] = (unsigned)(b >> 32);
+}
 
 #ifndef TPX_HOST_TEST  // device-only: wave helpers + boundary-scan kernels
 // wave helpers: 64-lane exclusive scan / reduction via shfl
@@ -1119,6 +1218,27 @@ __device__ __forceinline__ long long tpx_wave_exscan(long long v) {
 __device__ __forceinline__ long long tpx_wave_sum(long long v) {
     for (int o = 32; o; o >>= 1) v += __shfl_down((long long)v, o);
     return __shfl((long long)v, 0);
+}
+
+// 32-bit versions: half the shuffles, and room for packed fields
+__device__ __forceinline__ unsigned tpx_wave_exscan32(unsigned v, int lane) {
+    unsigned x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        unsigned y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    return x - v;  // exclusive
+}
+
+__device__ __forceinline__ unsigned tpx_wave_sum32(unsigned v) {
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;  // in every lane
+}
+
+// how many bits of a ballot belong to lanes below this one
+__device__ __forceinline__ unsigned tpx_lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
+               __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
 // Fused csv sink: tpx_stage_main formats kept rows itself. The table its
@@ -1175,41 +1295,39 @@ __device__ __forceinline__ char* tpx_wave_commit_csv(const TpxCsvSink& K,
     return K.text + base;
 }
 
-// per-lane scan of its 64-byte slice: counts quotes and newlines at even/odd
-// LOCAL quote parity. Coalesced uint4 loads when the slice is full.
-__device__ __forceinline__ void tpx_scan64(const char* __restrict__ data,
-                                           long long a, long long b,
-                                           int quotes_on,
-                                           long long* lq, long long* l0,
-                                           long long* l1) {
-    long long qq = 0, e0 = 0, e1 = 0;
-    if (b - a == TPX_CSV_LANE_BYTES && ((a & 15) == 0)) {
+// A wave reads its 4 KB chunk as four coalesced trips of 1 KiB: in trip t lane
+// l takes the 16 bytes at cb + 1024 t + 16 l, so one load instruction covers
+// one contiguous KiB. All four loads are issued before anything is classified.
+// Bytes at and after `size` come back as zero and are never read. `data` is
+// 16-byte aligned (an arena block or an allocation of its own).
+__device__ __forceinline__ void tpx_bs_load_chunk(const char* __restrict__ data,
+                                                  long long cb, long long size,
+                                                  int lane, uint4 v[4]) {
+    if (cb + TPX_CSV_CHUNK <= size) {
         #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            uint4 w = *(const uint4*)(data + a + v * 16);
-            unsigned words[4] = {w.x, w.y, w.z, w.w};
-            #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    unsigned ch = (words[k] >> (8 * s)) & 0xFF;
-                    if (quotes_on && ch == '"') ++qq;
-                    else if (ch == '\n') { if (qq & 1) ++e1; else ++e0; }
-                }
-        }
-    } else {
-        for (long long i = a; i < b; ++i) {
-            char ch = data[i];
-            if (quotes_on && ch == '"') ++qq;
-            else if (ch == '\n') { if (qq & 1) ++e1; else ++e0; }
+        for (int t = 0; t < 4; ++t)
+            v[t] = *(const uint4*)(data + cb + t * 1024 + lane * 16);
+    } else {  // the input's last chunk
+        #pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            long long k = cb + t * 1024 + lane * 16;
+            if (k + 16 <= size) {
+                v[t] = *(const uint4*)(data + k);
+            } else {
+                unsigned w[4];
+                tpx_bs_load_tail(data, k, size, w);
+                v[t] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
         }
     }
-    *lq = qq; *l0 = e0; *l1 = e1;
 }
 
-// wave-cooperative chunk stats: one wave per 4 KB chunk, lane i owns bytes
-// [i*64, i*64+64); lane parity composed by a wave scan — parallel-exact
-// restatement of the sequential quote-parity state machine.
+// wave-cooperative chunk stats: one wave per 4 KB chunk. Per trip every lane
+// counts its piece relative to the piece's own start (tpx_bs_count16); one
+// ballot of the lanes' quote-count parities gives each lane the parity at its
+// piece's start relative to the chunk's, which says whether its even / odd
+// counts go to c0 / c1 or the other way round: a parallel-exact restatement
+// of the sequential quote-parity state machine.
 extern "C" __global__ void tpx_csv_chunk_stats(const char* __restrict__ data,
                                                long long size, long long nchunks,
                                                long long* __restrict__ q,
@@ -1222,18 +1340,32 @@ extern "C" __global__ void tpx_csv_chunk_stats(const char* __restrict__ data,
     long long wstride = (long long)gridDim.x * wpb;
     for (long long c = (long long)blockIdx.x * wpb + wid; c < nchunks;
          c += wstride) {
-        long long a = c * TPX_CSV_CHUNK + (long long)lane * TPX_CSV_LANE_BYTES;
-        long long b = a + TPX_CSV_LANE_BYTES;
-        if (a > size) a = size;
-        if (b > size) b = size;
-        long long lq, l0, l1;
-        tpx_scan64(data, a, b, quotes_on, &lq, &l0, &l1);
-        long long pref = tpx_wave_exscan(lq);
-        bool odd = (pref & 1) != 0;
-        long long tot_q = tpx_wave_sum(lq);
-        long long tot0 = tpx_wave_sum(odd ? l1 : l0);
-        long long tot1 = tpx_wave_sum(odd ? l0 : l1);
-        if (lane == 0) { q[c] = tot_q; c0[c] = tot0; c1[c] = tot1; }
+        uint4 v[4];
+        tpx_bs_load_chunk(data, c * TPX_CSV_CHUNK, size, lane, v);
+        unsigned carry = 0;            // parity of the quotes of earlier trips
+        unsigned acc = 0, accq = 0;    // c0 | c1 << 16, and q, of this lane
+        #pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            unsigned nq, e, o;
+            tpx_bs_count16(v[t].x, v[t].y, v[t].z, v[t].w, quotes_on, &nq, &e,
+                           &o);
+            unsigned long long odd = __ballot(nq & 1u);
+            unsigned par = (carry ^ tpx_lanes_below(odd)) & 1u;
+            acc += par ? (o | e << 16) : (e | o << 16);
+            accq += nq;
+            carry ^= (unsigned)__popcll(odd);
+        }
+        // A byte is in one class at most, so a lane's three counts sum to at
+        // most its 64 bytes and the wave's to at most 4096 < 2^16: the c0
+        // field cannot carry into c1 (all-'\n' chunk: c0 = 4096), and q has a
+        // word to itself (all-'"' chunk: q = 4096). Three 13-bit fields do not
+        // fit one word, hence two sums; they are independent and overlap.
+        unsigned s = tpx_wave_sum32(acc), sq = tpx_wave_sum32(accq);
+        if (lane == 0) {
+            q[c] = (long long)sq;
+            c0[c] = (long long)(s & 0xFFFFu);
+            c1[c] = (long long)(s >> 16);
+        }
     }
 }
 
@@ -1256,6 +1388,63 @@ extern "C" __global__ void tpx_csv_select_counts(const long long* __restrict__ q
 // newline is kept even when it is the chunk's last boundary (base[c+1] ==
 // row_lo), so one call suffices for its range. Chunks at a range edge are
 // re-emitted by the neighbouring call — idempotent writes.
+// One pass over chunk c: `par0` = parity of every '"' byte before the chunk,
+// `rbase` = rows that end before it. Per trip: detect, one ballot for the
+// lanes' start parities, the mask of newlines outside quotes, the lanes' ranks
+// among the trip's rows, and each lane stores the end offsets of its rows.
+__device__ __forceinline__ void tpx_bs_emit_chunk(const char* __restrict__ data,
+                                                  long long size, long long c,
+                                                  unsigned par0, long long rbase,
+                                                  long long* __restrict__ row_offs,
+                                                  int quotes_on, int lane) {
+    long long cb = c * TPX_CSV_CHUNK;
+    uint4 v[4];
+    tpx_bs_load_chunk(data, cb, size, lane, v);
+    unsigned carry = par0 & 1u;
+    long long run = rbase;
+    #pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        tpx_bs_det d;
+        tpx_bs_detect(v[t].x, v[t].y, v[t].z, v[t].w, quotes_on, &d);
+        unsigned long long odd = __ballot(__popc(d.mq) & 1);
+        unsigned par = (carry ^ tpx_lanes_below(odd)) & 1u;
+        carry ^= (unsigned)__popcll(odd) & 1u;
+        unsigned r16 = tpx_bs_rows16(&d, par);
+        unsigned cnt = (unsigned)__popc(r16);
+        // rows shorter than 16 bytes are rare: with at most one row end per
+        // lane the ranks are a ballot's bit counts; otherwise a 32-bit exscan
+        // (a lane adds at most 16, the wave at most 1024)
+        unsigned ex, tot;
+        if (__ballot(cnt > 1u) == 0) {
+            unsigned long long one = __ballot(cnt != 0u);
+            ex = tpx_lanes_below(one);
+            tot = (unsigned)__popcll(one);
+        } else {
+            ex = tpx_wave_exscan32(cnt, lane);
+            tot = (unsigned)__builtin_amdgcn_readlane((int)(ex + cnt), 63);
+        }
+        long long idx = run + ex;
+        long long k = cb + t * 1024 + lane * 16;
+        while (r16) {
+            row_offs[1 + idx++] = k + __ffs((int)r16);  // position + 1
+            r16 &= r16 - 1;
+        }
+        run += tot;
+    }
+}
+
+// row_lo/row_hi restrict emission to the byte-chunks that write
+// row_offs[row_lo..row_hi], which is what the main kernel for rows
+// [row_lo,row_hi) reads, so the offsets for one main-kernel chunk can be emitted
+// just-in-time on that chunk's stream (overlapping the previous chunk's main).
+// row_offs[row_lo] is the end of row row_lo-1: the byte-chunk holding that
+// newline is kept even when it is the chunk's last boundary (base[c+1] ==
+// row_lo), so one call suffices for its range. Chunks at a range edge are
+// re-emitted by the neighbouring call — idempotent writes.
+//
+// A wave owns chunks first, first + wstride, ...; a ranged call skips most of
+// them. Lane i tests the wave's i-th chunk, so 64 chunks cost one round trip
+// to `base`, not one each, and the wave then walks the ballot's set bits.
 extern "C" __global__ void tpx_csv_emit_rows(const char* __restrict__ data,
                                              long long size, long long nchunks,
                                              const long long* __restrict__ qscan,
@@ -1268,44 +1457,20 @@ extern "C" __global__ void tpx_csv_emit_rows(const char* __restrict__ data,
     int wpb = blockDim.x >> 6;
     long long wstride = (long long)gridDim.x * wpb;
     if (blockIdx.x == 0 && threadIdx.x == 0 && row_lo == 0) row_offs[0] = 0;
-    for (long long c = (long long)blockIdx.x * wpb + wid; c < nchunks;
-         c += wstride) {
-        if (base[c] >= row_hi) continue;
-        if (c + 1 < nchunks && base[c + 1] < row_lo) continue;
-        long long a = c * TPX_CSV_CHUNK + (long long)lane * TPX_CSV_LANE_BYTES;
-        long long b = a + TPX_CSV_LANE_BYTES;
-        if (a > size) a = size;
-        if (b > size) b = size;
-        long long lq, l0, l1;
-        tpx_scan64(data, a, b, quotes_on, &lq, &l0, &l1);
-        long long pref_q = tpx_wave_exscan(lq);
-        long long start_par = (qscan[c] + pref_q) & 1;
-        long long sel = start_par ? l1 : l0;   // valid newlines in this lane
-        long long lane_base = base[c] + tpx_wave_exscan(sel);
-        // second pass: emit offsets for valid newlines (vector loads when full)
-        long long qq = 0, idx = lane_base;
-        if (b - a == TPX_CSV_LANE_BYTES && ((a & 15) == 0)) {
-            #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                uint4 w = *(const uint4*)(data + a + v * 16);
-                unsigned words[4] = {w.x, w.y, w.z, w.w};
-                #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    #pragma unroll
-                    for (int s2 = 0; s2 < 4; ++s2) {
-                        unsigned ch = (words[k] >> (8 * s2)) & 0xFF;
-                        if (quotes_on && ch == '"') ++qq;
-                        else if (ch == '\n' && (((qq + start_par) & 1) == 0))
-                            row_offs[1 + idx++] = a + v * 16 + k * 4 + s2 + 1;
-                    }
-            }
-        } else {
-            for (long long i = a; i < b; ++i) {
-                char ch = data[i];
-                if (quotes_on && ch == '"') ++qq;
-                else if (ch == '\n' && (((qq + start_par) & 1) == 0))
-                    row_offs[1 + idx++] = i + 1;
-            }
+    for (long long cg = (long long)blockIdx.x * wpb + wid; cg < nchunks;
+         cg += 64 * wstride) {
+        long long mc = cg + lane * wstride;
+        bool want = false;
+        if (mc < nchunks)
+            want = base[mc] < row_hi &&
+                   !(mc + 1 < nchunks && base[mc + 1] < row_lo);
+        unsigned long long todo = __ballot(want);
+        while (todo) {
+            int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            long long c = cg + i * wstride;
+            tpx_bs_emit_chunk(data, size, c, (unsigned)qscan[c] & 1u, base[c],
+                              row_offs, quotes_on, lane);
         }
     }
 }
