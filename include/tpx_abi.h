@@ -170,6 +170,62 @@ int64_t tpx_stage_execute_col(tpx_stage* stage, void* const* slots,
                               int64_t in_bytes, int64_t first_global_row,
                               int64_t flags, tpx_result* result);
 
+/* ---- device-resident cache() partitions ------------------------------------------
+ * A tpx_table is one dense columnar (Arrow-layout) partition in HBM that the
+ * library owns: the kept rows of one stage execute, packed on the device into
+ * exactly the slots tpx_stage_execute_col reads. Its memory is its own
+ * (hipMalloc), not workspace-arena memory, so it outlives later executes; it
+ * lives on the device that was current when it was made, and every call
+ * below selects that device for its own duration. */
+typedef struct tpx_table tpx_table;
+
+/* Return code of the cache executes when the table's memory cannot be had
+ * (hipMalloc failed, or the byte cap of the TPX_TABLE_MAX_BYTES environment
+ * variable — read once — was exceeded). No table is returned, never a partial
+ * one; the caller falls back to a host cache. */
+#define TPX_E_TABLE_ALLOC 2
+
+/* Cache-mode executes over host / device-resident CSV bytes: the stage runs
+ * as in tpx_stage_execute_csv(_dev), but instead of serializing kept rows
+ * and copying them out, the pack kernels leave them in *table. The stage
+ * must have a mem sink, no aggregate and no fused csv sink. Of the normal
+ * output only result->out_num_rows and result->out_row_indices (the global
+ * input row index of each table row, 8 bytes per row) are filled; out_data
+ * and out_row_offsets stay NULL. Exceptions are returned exactly as by the
+ * plain executes. *table is NULL when the input holds no rows. */
+int64_t tpx_stage_cache_csv(tpx_stage* stage,
+                            const uint8_t* csv_bytes, int64_t size,
+                            int64_t first_global_row,
+                            tpx_result* result, tpx_table** table);
+int64_t tpx_stage_cache_csv_dev(tpx_stage* stage,
+                                uint64_t dev_bytes, int64_t size,
+                                int64_t first_global_row,
+                                tpx_result* result, tpx_table** table);
+
+/* Rows / device bytes of a table; -1 for NULL. */
+int64_t tpx_table_rows(const tpx_table* table);
+int64_t tpx_table_bytes(const tpx_table* table);
+
+/* Fill `slots` with the table's 3 device pointers per column, in the layout
+ * tpx_stage_execute_col takes, and (if non-NULL) `slot_bytes` with the bytes
+ * each holds (0 for a NULL slot). Returns 3 * ncols, or -1 if n_slots is
+ * smaller than that or table is NULL. */
+int64_t tpx_table_slots(const tpx_table* table, void** slots,
+                        int64_t* slot_bytes, int64_t n_slots);
+
+/* Copy the columns to host buffers (lazy materialisation): host_slots[k]
+ * receives slot k's bytes (tpx_table_slots' slot_bytes[k]); NULL entries are
+ * skipped. Returns 0 on success. */
+int64_t tpx_table_download(const tpx_table* table, void* const* host_slots,
+                           int64_t n_slots);
+
+void tpx_table_free(tpx_table* table);
+
+/* Cumulative per-process byte counts of the host<->device copies the library
+ * has issued (device-to-device copies count as neither). Either pointer may
+ * be NULL. Works without a GPU. Returns 0. */
+int64_t tpx_xfer_stats(int64_t* h2d_bytes, int64_t* d2h_bytes);
+
 /* Generated-source introspection (debug / judge). Returns the HIP source the stage
  * was compiled from (owned by the stage). */
 const char* tpx_stage_source(const tpx_stage* stage);

@@ -34,9 +34,12 @@ _RT_HEADER_CACHE = None
 def runtime_header() -> str:
     global _RT_HEADER_CACHE
     if _RT_HEADER_CACHE is None:
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                            "csrc", "tpx_rt.hip.h")
-        _RT_HEADER_CACHE = open(path).read()
+        here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+        # tpx_cache.hip.h: the fixed cache()-pack kernels, after the runtime
+        # they build on (wave scans); part of every stage's source
+        _RT_HEADER_CACHE = (
+            open(os.path.join(here, "tpx_rt.hip.h")).read() + "\n" +
+            open(os.path.join(here, "tpx_cache.hip.h")).read())
     return _RT_HEADER_CACHE
 
 

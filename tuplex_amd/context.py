@@ -50,6 +50,42 @@ class CachedSource:
         self.columns = columns
 
 
+class DeviceCachedSource:
+    """cache() materialization that stayed in HBM: one columnar device table
+    (engine.DeviceTable, with its host row keys) per executed chunk, plus
+    what CachedSource holds on the host — here the `extras`, (key, row) pairs
+    of rows stage 1 diverted and the interpreter replayed, and the stored
+    pending exceptions with their replayer. Tables are freed with the source.
+    host_source() materialises everything into a CachedSource (lazy download,
+    kept afterwards)."""
+    kind = "dcached"
+
+    def __init__(self, tables, extras, col_types, device, pending, replayer,
+                 pre_ops, columns):
+        self.tables = tables
+        self.extras = extras
+        self.col_types = col_types
+        self.device = device
+        self.pending = pending
+        self.replayer = replayer
+        self.pre_ops = pre_ops
+        self.columns = columns
+        self._host = None
+
+    def host_source(self):
+        if self._host is None:
+            pairs = list(self.extras)
+            for tab in self.tables:
+                if tab.rows:
+                    pairs.extend(zip(tab.keys.tolist(), tab.host_rows()))
+            pairs.sort(key=lambda t: t[0])
+            self._host = CachedSource([v for _, v in pairs],
+                                      [k for k, _ in pairs], self.pending,
+                                      self.replayer, self.pre_ops,
+                                      self.columns)
+        return self._host
+
+
 class OrcSource:
     kind = "orc"
 
@@ -118,13 +154,20 @@ class Context:
         return ""
 
     # ---- execution ----------------------------------------------------------
-    def _execute(self, ds: DataSet, sink=None, keep_exceptions=False):
+    def _execute(self, ds: DataSet, sink=None, keep_exceptions=False,
+                 device_cache=False):
+        """device_cache: a cache() whose pipeline engine.cache_eligibility
+        accepted — the csv run leaves its kept rows in HBM
+        (outcome.device_cache) instead of returning them."""
         src = ds._source
+        if src.kind == "dcached" and sink is not None:
+            # tocsv from a cached source stays host-formatted (below)
+            src = src.host_source()
         # mid-pipeline duplicate-key join: split the pipeline at the join
         # (PhysicalPlan stage-split analog) so stage 1 runs the GPU terminal
         # 1:N expansion and stage 2 continues compiled from the materialized
         # rows; exceptions stay deferred through the CachedSource replayer
-        if src.kind in ("mem", "csv", "cached"):
+        if src.kind in ("mem", "csv", "cached", "dcached"):
             from . import plan as _plan
             cut = _plan.find_dup_join_split(ds._ops)
             if cut is not None:
@@ -152,6 +195,9 @@ class Context:
         elif src.kind == "cached":
             outcome = engine.run_cached(self, src, ds._ops,
                                         keep_exceptions=keep_exceptions)
+        elif src.kind == "dcached":
+            outcome = engine.run_dcached(self, src, ds._ops,
+                                         keep_exceptions=keep_exceptions)
         elif src.kind == "orc":
             from . import orcio
             outcome = orcio.run_orc(self, src, ds._ops, sink,
@@ -159,7 +205,8 @@ class Context:
         else:
             from . import csvio
             outcome = csvio.run_csv(self, src, ds._ops, sink,
-                                    keep_exceptions=keep_exceptions)
+                                    keep_exceptions=keep_exceptions,
+                                    device_cache=device_cache)
         self.metrics.data.update({
             "mode": outcome.mode,
             **{k: v for k, v in outcome.metrics.items()},

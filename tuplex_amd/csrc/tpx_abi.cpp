@@ -20,12 +20,14 @@
 #include <hip/hiprtc.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <unistd.h>
 #include <functional>
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <sstream>
 #include <string>
@@ -39,7 +41,19 @@ static void set_err(const std::string& e) { g_err = e; }
 
 extern "C" const char* tpx_last_error(void) { return g_err.c_str(); }
 
-extern "C" int64_t tpx_version(void) { return (1 << 16) | 0; }
+extern "C" int64_t tpx_version(void) { return (1 << 16) | 1; }
+
+// cumulative host<->device copy bytes (tpx_xfer_stats): every copy the
+// library issues is counted where it is issued
+static std::atomic<long long> g_h2d_bytes{0}, g_d2h_bytes{0};
+static inline void xfer_h2d(size_t n) { g_h2d_bytes += (long long)n; }
+static inline void xfer_d2h(size_t n) { g_d2h_bytes += (long long)n; }
+
+extern "C" int64_t tpx_xfer_stats(int64_t* h2d_bytes, int64_t* d2h_bytes) {
+    if (h2d_bytes) *h2d_bytes = g_h2d_bytes.load();
+    if (d2h_bytes) *d2h_bytes = g_d2h_bytes.load();
+    return 0;
+}
 
 extern "C" int64_t tpx_device_count(void) {
     int n = 0;
@@ -157,6 +171,7 @@ struct tpx_stage {
     hipFunction_t k_pair_scan_block = nullptr, k_pair_scan_sums = nullptr;
     hipFunction_t k_pair_scan_add = nullptr;
     hipFunction_t k_csv_gather = nullptr;
+    hipFunction_t k_cache_fixed = nullptr, k_cache_gather = nullptr;
     hipFunction_t k_csv_chunk = nullptr, k_csv_sel = nullptr, k_csv_rows = nullptr;
     hipFunction_t k_red_f64 = nullptr, k_red_f64_fin = nullptr;
     hipFunction_t k_red_i64 = nullptr, k_red_i64_fin = nullptr;
@@ -270,6 +285,8 @@ extern "C" tpx_stage* tpx_stage_compile(const char* hip_source,
         {"tpx_pair_scan_sums", &st->k_pair_scan_sums, true},
         {"tpx_pair_scan_add", &st->k_pair_scan_add, true},
         {"tpx_csv_gather", &st->k_csv_gather, st->desc.fusedcsv != 0},
+        {"tpx_cache_pack_fixed", &st->k_cache_fixed, false},
+        {"tpx_cache_gather_str", &st->k_cache_gather, false},
         {"tpx_csv_chunk_stats", &st->k_csv_chunk, false},
         {"tpx_csv_select_counts", &st->k_csv_sel, false},
         {"tpx_csv_emit_rows", &st->k_csv_rows, false},
@@ -476,12 +493,246 @@ static int dev_scan(tpx_stage* st, hipStream_t stream, long long* d_in,
     }
     if (!total) return 0;  // caller does not need the total
     long long last_out = 0, last_in = 0;
+    xfer_d2h(16);
     HIP_CHECK(hipMemcpyAsync(&last_out, d_out + (n - 1), 8,
                              hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(&last_in, d_in + (n - 1), 8, hipMemcpyDeviceToHost,
                              stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     *total = last_out + last_in;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// device-resident cache() partitions (tpx_table): dense Arrow-layout columns
+// packed on the device from a stage's outv slots (csrc/tpx_cache.hip.h)
+
+struct tpx_table {
+    int dev = 0;
+    long long rows = 0;
+    size_t bytes = 0;                 // device bytes held (both blocks)
+    void* fixed = nullptr;            // values, bool arrays, masks, offsets
+    void* strs = nullptr;             // string data of every str column
+    std::vector<void*> slots;         // 3 per column, tpx_stage_execute_col layout
+    std::vector<long long> slot_bytes;
+};
+
+// selects a table's device for the scope of a call
+struct DeviceScope {
+    int prev = 0;
+    bool switched = false;
+    explicit DeviceScope(int dev) {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev)
+            switched = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
+extern "C" void tpx_table_free(tpx_table* t) {
+    if (!t) return;
+    {
+        DeviceScope ds(t->dev);
+        if (t->fixed) (void)hipFree(t->fixed);
+        if (t->strs) (void)hipFree(t->strs);
+    }
+    delete t;
+}
+
+extern "C" int64_t tpx_table_rows(const tpx_table* t) {
+    return t ? t->rows : -1;
+}
+
+extern "C" int64_t tpx_table_bytes(const tpx_table* t) {
+    return t ? (int64_t)t->bytes : -1;
+}
+
+extern "C" int64_t tpx_table_slots(const tpx_table* t, void** slots,
+                                   int64_t* slot_bytes, int64_t n_slots) {
+    if (!t || !slots || n_slots < (int64_t)t->slots.size()) {
+        set_err("tpx_table_slots: no table, or too few slots");
+        return -1;
+    }
+    for (size_t k = 0; k < t->slots.size(); ++k) {
+        slots[k] = t->slots[k];
+        if (slot_bytes) slot_bytes[k] = t->slot_bytes[k];
+    }
+    return (int64_t)t->slots.size();
+}
+
+extern "C" int64_t tpx_table_download(const tpx_table* t,
+                                      void* const* host_slots,
+                                      int64_t n_slots) {
+    if (!t || !host_slots || n_slots < (int64_t)t->slots.size()) {
+        set_err("tpx_table_download: no table, or too few slots");
+        return -1;
+    }
+    DeviceScope ds(t->dev);
+    for (size_t k = 0; k < t->slots.size(); ++k) {
+        if (!host_slots[k] || !t->slots[k] || !t->slot_bytes[k]) continue;
+        xfer_d2h((size_t)t->slot_bytes[k]);
+        HIP_CHECK(hipMemcpy(host_slots[k], t->slots[k],
+                            (size_t)t->slot_bytes[k], hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// descriptor of tpx_cache_pack_fixed (csrc/tpx_cache.hip.h: tpx_cp_desc)
+struct CpDesc {
+    const void* src;
+    void* dst;
+    const void* nul;
+    long long kind;
+};
+enum { CP_VAL8 = 0, CP_BOOL = 1, CP_MASK = 2, CP_LEN = 3 };
+
+// Pack the kept rows of an n-row execute (keep, rank = exclusive scan of keep,
+// m = total kept, outv = the host copy of the slot table) into a new table.
+// Runs and completes on `stream` before it returns: the string pointers in
+// outv refer to input and heap memory that the next execute reuses. Returns 0,
+// -1 (error), or TPX_E_TABLE_ALLOC with nothing left allocated.
+static int64_t pack_table(tpx_stage* st, hipStream_t stream, int dev,
+                          const std::vector<void*>& outv, void* d_keep,
+                          void* d_rank, long long n, long long row0,
+                          long long m, void** d_rowkey_out, tpx_table** out) {
+    const StageDesc& D = st->desc;
+    if (!st->k_cache_fixed || !st->k_cache_gather) {
+        set_err("stage compiled without the cache pack kernels");
+        return -1;
+    }
+    static long long env_cap = [] {
+        const char* e = getenv("TPX_TABLE_MAX_BYTES");
+        return e ? atoll(e) : -1LL;
+    }();
+    int nout = (int)D.out_cols.size();
+    // every array starts 256-aligned and has 128 B of slack behind it (the
+    // columnar loader's string reads may run a word past a cell)
+    auto padded = [](size_t b) { return (b + 128 + 255) & ~(size_t)255; };
+    std::unique_ptr<tpx_table> T(new tpx_table());
+    T->dev = dev;
+    T->rows = m;
+    T->slots.assign((size_t)nout * 3, nullptr);
+    T->slot_bytes.assign((size_t)nout * 3, 0);
+    std::vector<size_t> foff((size_t)nout * 3, 0);
+    size_t fixed_bytes = 0;
+    for (int k = 0; k < nout; ++k) {
+        const ColDesc& c = D.out_cols[(size_t)k];
+        size_t b0 = c.kind == K_STR ? ((size_t)m + 1) * 8
+                  : c.kind == K_BOOL ? (size_t)m : (size_t)m * 8;
+        T->slot_bytes[(size_t)k * 3] = (long long)b0;
+        foff[(size_t)k * 3] = fixed_bytes;
+        fixed_bytes += padded(b0);
+        if (c.opt) {
+            T->slot_bytes[(size_t)k * 3 + 2] = m;
+            foff[(size_t)k * 3 + 2] = fixed_bytes;
+            fixed_bytes += padded((size_t)m);
+        }
+    }
+    if (env_cap >= 0 && (long long)fixed_bytes > env_cap) {
+        set_err("cache table exceeds TPX_TABLE_MAX_BYTES");
+        return TPX_E_TABLE_ALLOC;
+    }
+    if (hipMalloc(&T->fixed, fixed_bytes ? fixed_bytes : 256) != hipSuccess) {
+        T->fixed = nullptr;
+        set_err("cache table hipMalloc failed");
+        return TPX_E_TABLE_ALLOC;
+    }
+    // from here on every error path frees the blocks
+    struct Guard {
+        tpx_table* t;
+        ~Guard() {
+            if (!t) return;
+            if (t->fixed) (void)hipFree(t->fixed);
+            if (t->strs) (void)hipFree(t->strs);
+            t->fixed = t->strs = nullptr;
+        }
+    } guard{T.get()};
+
+    std::vector<CpDesc> descs;
+    std::vector<void*> klen((size_t)nout, nullptr);  // kept lengths, m+1, last 0
+    for (int k = 0; k < nout; ++k) {
+        const ColDesc& c = D.out_cols[(size_t)k];
+        void* s0 = (char*)T->fixed + foff[(size_t)k * 3];
+        T->slots[(size_t)k * 3] = s0;
+        if (c.kind == K_STR) {
+            klen[(size_t)k] = g_arena[dev].take(((size_t)m + 1) * 8);
+            if (!klen[(size_t)k]) return -1;
+            HIP_CHECK(hipMemsetAsync(klen[(size_t)k], 0, ((size_t)m + 1) * 8,
+                                     stream));
+            descs.push_back({outv[(size_t)k * 3 + 1], klen[(size_t)k],
+                             c.opt ? outv[(size_t)k * 3 + 2] : nullptr,
+                             CP_LEN});
+        } else {
+            descs.push_back({outv[(size_t)k * 3], s0, nullptr,
+                             c.kind == K_BOOL ? CP_BOOL : CP_VAL8});
+        }
+        if (c.opt) {
+            void* s2 = (char*)T->fixed + foff[(size_t)k * 3 + 2];
+            T->slots[(size_t)k * 3 + 2] = s2;
+            descs.push_back({outv[(size_t)k * 3 + 2], s2, nullptr, CP_MASK});
+        }
+    }
+    ARENA_TAKE(d_desc, descs.size() * sizeof(CpDesc) + 8);
+    ARENA_TAKE(d_rowkey, ((size_t)m + 1) * 8);
+    xfer_h2d(descs.size() * sizeof(CpDesc));
+    HIP_CHECK(hipMemcpyAsync(d_desc, descs.data(),
+                             descs.size() * sizeof(CpDesc),
+                             hipMemcpyHostToDevice, stream));
+    {
+        int ndesc = (int)descs.size();
+        unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+        if (grid < 1) grid = 1;
+        void* args[] = {&d_keep, &d_rank, &n, &row0, &d_desc, &ndesc,
+                        &d_rowkey};
+        if (launch(st->k_cache_fixed, grid, 256, stream, args)) return -1;
+    }
+    // string offsets: exclusive scan of the kept lengths over m+1 entries —
+    // the zero behind the last row makes offsets[m] the column's byte total
+    std::vector<long long> stotal((size_t)nout, 0);
+    size_t str_bytes = 0;
+    std::vector<size_t> soff((size_t)nout, 0);
+    for (int k = 0; k < nout; ++k) {
+        if (D.out_cols[(size_t)k].kind != K_STR) continue;
+        if (dev_scan(st, stream, (long long*)klen[(size_t)k],
+                     (long long*)T->slots[(size_t)k * 3], m + 1,
+                     &stotal[(size_t)k]))
+            return -1;
+        soff[(size_t)k] = str_bytes;
+        str_bytes += padded((size_t)stotal[(size_t)k]);
+        T->slot_bytes[(size_t)k * 3 + 1] = stotal[(size_t)k];
+    }
+    if (str_bytes) {
+        if (env_cap >= 0 && (long long)(fixed_bytes + str_bytes) > env_cap) {
+            set_err("cache table exceeds TPX_TABLE_MAX_BYTES");
+            return TPX_E_TABLE_ALLOC;
+        }
+        if (hipMalloc(&T->strs, str_bytes) != hipSuccess) {
+            T->strs = nullptr;
+            set_err("cache table hipMalloc failed");
+            return TPX_E_TABLE_ALLOC;
+        }
+    }
+    for (int k = 0; k < nout; ++k) {
+        const ColDesc& c = D.out_cols[(size_t)k];
+        if (c.kind != K_STR) continue;
+        void* data = (char*)T->strs + soff[(size_t)k];
+        T->slots[(size_t)k * 3 + 1] = data;
+        if (!stotal[(size_t)k]) continue;
+        long long nb = (n + 63) / 64;  // one wave per batch, 4 per block
+        unsigned grid = (unsigned)std::min<long long>((nb + 3) / 4, 8192);
+        if (grid < 1) grid = 1;
+        void* sptr = outv[(size_t)k * 3];
+        void* slen = outv[(size_t)k * 3 + 1];
+        void* snull = c.opt ? outv[(size_t)k * 3 + 2] : nullptr;
+        void* offs = T->slots[(size_t)k * 3];
+        void* args[] = {&d_keep, &d_rank, &n, &sptr, &slen, &snull, &offs,
+                        &data};
+        if (launch(st->k_cache_gather, grid, 256, stream, args)) return -1;
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    T->bytes = fixed_bytes + str_bytes;
+    guard.t = nullptr;
+    *d_rowkey_out = d_rowkey;
+    *out = T.release();
     return 0;
 }
 
@@ -504,9 +755,17 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                         long long row0, long long in_bytes, tpx_result* res,
                         const PayloadSrc& psrc, hipStream_t stream,
                         int64_t flags = 0, const PreChunkFn* pre_chunk = nullptr,
-                        const std::vector<void*>* in_tab = nullptr) {
+                        const std::vector<void*>* in_tab = nullptr,
+                        tpx_table** cache_out = nullptr) {
     const StageDesc& D = st->desc;
     int dev = cur_device();
+    // cache mode: kept rows are packed into a device table (pack_table)
+    // instead of being serialized by k_write — needs the columnar outv slots
+    if (cache_out &&
+        (D.fusedcsv || D.sink != "mem" || !D.agg.empty() || !D.aggby.empty())) {
+        set_err("cache execute: stage needs a plain mem sink");
+        return -1;
+    }
     Persist& P = g_persist[dev];
     res->in_num_rows = n;
     EventPool& EP = g_events[dev];
@@ -543,6 +802,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
             }
         d_outv = g_arena[dev].take(outv.size() * sizeof(void*) + 8);
         if (!d_outv) return -1;
+        xfer_h2d(outv.size() * sizeof(void*));
         HIP_CHECK(hipMemcpyAsync(d_outv, outv.data(),
                                  outv.size() * sizeof(void*),
                                  hipMemcpyHostToDevice, stream));
@@ -574,7 +834,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     bool mem_sink = D.sink == "mem";
     int C = 1;
     if (D.agg.empty() && D.aggby.empty() && n >= (1 << 20) &&
-        (d_offs || in_tab)) {
+        (d_offs || in_tab) && !cache_out) {  // the pack takes the C==1 path
         static int env_c = [] {
             const char* e = getenv("TPX_CHUNKS");
             int v = e ? atoi(e) : 4;
@@ -640,6 +900,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         }
         void* blk = g_arena[dev].take(ovall.size() * sizeof(void*) + 8);
         if (!blk) return -1;
+        xfer_h2d(ovall.size() * sizeof(void*));
         HIP_CHECK(hipMemcpyAsync(blk, ovall.data(), ovall.size() * sizeof(void*),
                                  hipMemcpyHostToDevice, stream));
         for (int c = 1; c < C; ++c)
@@ -666,6 +927,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         }
         void* blk = g_arena[dev].take(iall.size() * sizeof(void*) + 8);
         if (!blk) return -1;
+        xfer_h2d(iall.size() * sizeof(void*));
         HIP_CHECK(hipMemcpyAsync(blk, iall.data(), iall.size() * sizeof(void*),
                                  hipMemcpyHostToDevice, stream));
         for (int c = 1; c < C; ++c)
@@ -726,6 +988,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         }
         void* blk = g_arena[dev].take(pall.size() * sizeof(void*) + 8);
         if (!blk) return -1;
+        xfer_h2d(pall.size() * sizeof(void*));
         HIP_CHECK(hipMemcpyAsync(blk, pall.data(),
                                  pall.size() * sizeof(void*),
                                  hipMemcpyHostToDevice, stream));
@@ -829,6 +1092,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
             }
             void* blk = g_arena[dev].take(sizeof tab);
             if (!blk) return -1;
+            xfer_h2d(sizeof tab);
             HIP_CHECK(hipMemcpyAsync(blk, tab, sizeof tab,
                                      hipMemcpyHostToDevice, stream));
             for (int c = 0; c < C; ++c)
@@ -911,6 +1175,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                 if (nblocks > 1 && launch(st->k_pair_scan_add,
                                           (unsigned)nblocks, 256, sc, a3))
                     return -1;
+                xfer_d2h(16);
                 HIP_CHECK(hipMemcpyAsync((char*)pinned(dev) + 16 * c, slot, 16,
                                          hipMemcpyDeviceToHost, sc));
                 hipEventRecord(cev[(size_t)c * 4 + 1], sc);
@@ -1003,6 +1268,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         // sync below covers C==1)
         unsigned long long* counters =
             (unsigned long long*)((char*)pinned(dev) + 256);
+        xfer_d2h(160);
         HIP_CHECK(hipMemcpyAsync(counters, P.counters, 160,
                                  hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -1100,6 +1366,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                           &tvals, &tmask, &d_used, &d_ovf};
             if (launch(kfill, grid2, 256, stream, a1)) return -1;
             unsigned long long st8[2] = {0, 0};
+            xfer_d2h(16);
             HIP_CHECK(hipMemcpyAsync(st8, d_hk_state, 16,
                                      hipMemcpyDeviceToHost, stream));
             HIP_CHECK(hipStreamSynchronize(stream));
@@ -1125,10 +1392,12 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         }
         hipEventRecord(ev2, stream);
         unsigned long long nout = 0;
+        xfer_d2h(8);
         HIP_CHECK(hipMemcpyAsync(&nout, d_oidx, 8, hipMemcpyDeviceToHost,
                                  stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         std::vector<long long> tri((size_t)nout * 3);
+        xfer_d2h((size_t)nout * 24);
         if (nout)
             HIP_CHECK(hipMemcpy(tri.data(), d_tri, (size_t)nout * 24,
                                 hipMemcpyDeviceToHost));
@@ -1137,6 +1406,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         for (unsigned long long e = 0; e < nout; ++e) {
             long long len = tri[e * 3 + 1];
             std::string key((size_t)len, 0);
+            xfer_d2h((size_t)len);
             if (len)
                 HIP_CHECK(hipMemcpy(&key[0], (void*)(uintptr_t)tri[e * 3],
                                     (size_t)len, hipMemcpyDeviceToHost));
@@ -1213,6 +1483,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                           &d_used, &d_ovf, &d_scnt, &d_sval};
             if (launch(kfill, grid2, 256, stream, a1)) return -1;
             unsigned long long st8[2] = {0, 0};
+            xfer_d2h(16);
             HIP_CHECK(hipMemcpyAsync(st8, d_hk_state, 16, hipMemcpyDeviceToHost,
                                      stream));
             HIP_CHECK(hipStreamSynchronize(stream));
@@ -1241,6 +1512,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         }
         hipEventRecord(ev2, stream);
         unsigned long long nout_rows = 0;
+        xfer_d2h(8);
         HIP_CHECK(hipMemcpyAsync(&nout_rows, d_oidx, 8, hipMemcpyDeviceToHost,
                                  stream));
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -1249,6 +1521,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         res->out_num_rows = total;
         res->out_data = (uint8_t*)malloc((size_t)res->out_size);
         ((int64_t*)res->out_data)[0] = total;
+        xfer_d2h((size_t)total * 16);
         if (total)
             HIP_CHECK(hipMemcpy(res->out_data + 8, (char*)d_out + 8,
                                 (size_t)total * 16, hipMemcpyDeviceToHost));
@@ -1277,6 +1550,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         hipEventRecord(evs1, stream);
         hipEventRecord(ev2, stream);
         long long bits = 0;
+        xfer_d2h(8);
         HIP_CHECK(hipMemcpyAsync(&bits, d_res8, 8, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         res->out_size = 16;
@@ -1289,6 +1563,33 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
         res->out_row_offsets[1] = 16;
         res->out_row_indices = (int64_t*)malloc(8);
         res->out_row_indices[0] = 0;
+    } else if (cache_out) {
+        // rank of every row, then the pack; only the row keys go to the host
+        d_keep_scan = g_arena[dev].take((size_t)n * 8);
+        if (!d_keep_scan) return -1;
+        if (dev_scan(st, stream, (long long*)d_keep01, (long long*)d_keep_scan,
+                     n, &total_rows))
+            return -1;
+        hipEventRecord(evs1, stream);
+        void* d_rowkey = nullptr;
+        int64_t prc = pack_table(st, stream, dev, outv, d_keep, d_keep_scan, n,
+                                 row0, total_rows, &d_rowkey, cache_out);
+        if (prc != 0) return prc;
+        hipEventRecord(ev2, stream);
+        res->out_num_rows = total_rows;
+        res->out_row_indices = (int64_t*)malloc(((size_t)total_rows + 1) * 8);
+        if (total_rows) {
+            xfer_d2h((size_t)total_rows * 8);
+            if (hipMemcpyAsync(res->out_row_indices, d_rowkey,
+                               (size_t)total_rows * 8, hipMemcpyDeviceToHost,
+                               stream) != hipSuccess) {
+                set_err("row key copy failed");
+                tpx_table_free(*cache_out);
+                *cache_out = nullptr;
+                return -1;
+            }
+        }
+        res->bytes_out = (int64_t)(*cache_out)->bytes;
     } else {
     long long out_total;
     if (sink_done) {
@@ -1330,6 +1631,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     }
     // header + sentinel are host-written (the kernels write only row entries)
     long long sentinel = out_total;
+    xfer_h2d(mem_sink ? 16 : 8);
     HIP_CHECK(hipMemcpyAsync((char*)d_out_offs + total_rows * 8, &sentinel, 8,
                              hipMemcpyHostToDevice, stream));
     if (mem_sink)
@@ -1341,6 +1643,8 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     res->out_size = out_total;
     res->out_num_rows = total_rows;
     if (!(flags & 2)) {
+        xfer_d2h((size_t)out_total + ((size_t)total_rows + 1) * 8 +
+                 (size_t)total_rows * 8);
         res->out_data = (uint8_t*)malloc((size_t)out_total);
         HIP_CHECK(hipMemcpyAsync(res->out_data, d_out, (size_t)out_total,
                                  hipMemcpyDeviceToHost, stream));
@@ -1357,6 +1661,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
     res->bytes_out = out_total;
     }
     std::vector<ExcRec> excs((size_t)exc_count);
+    xfer_d2h((size_t)exc_count * sizeof(ExcRec));
     if (exc_count)
         HIP_CHECK(hipMemcpyAsync(excs.data(), P.exc,
                                  (size_t)exc_count * sizeof(ExcRec),
@@ -1397,6 +1702,7 @@ static int64_t run_core(tpx_stage* st, void* d_in, void* d_offs, long long n,
                 // device-only input: copy the raw line back (rare path)
                 long long len = excs[i].off_end - excs[i].off_start;
                 fetched.emplace_back((size_t)len);
+                xfer_d2h((size_t)len);
                 HIP_CHECK(hipMemcpy(fetched.back().data(),
                                     (const char*)d_in + excs[i].off_start,
                                     (size_t)len, hipMemcpyDeviceToHost));
@@ -1480,6 +1786,7 @@ extern "C" int64_t tpx_stage_execute_col(tpx_stage* st, void* const* slots,
     res->bytes_in = in_bytes;
     if (n_rows == 0) { empty_result(res, st->desc.sink == "mem"); return 0; }
     ARENA_TAKE(d_tab, (size_t)n_slots * sizeof(void*) + 8);
+    xfer_h2d((size_t)n_slots * sizeof(void*));
     HIP_CHECK(hipMemcpyAsync(d_tab, slots, (size_t)n_slots * sizeof(void*),
                              hipMemcpyHostToDevice, stream));
     PayloadSrc psrc{nullptr, nullptr, 0};
@@ -1517,6 +1824,7 @@ extern "C" int64_t tpx_stage_execute(tpx_stage* st, const tpx_partition* parts,
         long long byte_base = 0, row_base = 0;
         for (int64_t p = 0; p < n_parts; ++p) {
             const tpx_partition& P = parts[p];
+            xfer_h2d((size_t)P.size);
             HIP_CHECK(hipMemcpyAsync((char*)d_in + byte_base, P.data,
                                      (size_t)P.size, hipMemcpyHostToDevice, stream));
             for (long long r = 0; r < P.num_rows; ++r)
@@ -1525,6 +1833,7 @@ extern "C" int64_t tpx_stage_execute(tpx_stage* st, const tpx_partition* parts,
             row_base += P.num_rows;
         }
         offs[(size_t)n] = byte_base;
+        xfer_h2d(((size_t)n + 1) * 8);
         HIP_CHECK(hipMemcpyAsync(d_offs, offs.data(), ((size_t)n + 1) * 8,
                                  hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -1547,7 +1856,8 @@ extern "C" int64_t tpx_stage_execute(tpx_stage* st, const tpx_partition* parts,
 static int64_t csv_boundary_and_core(tpx_stage* st, void* d_in_p, long long size,
                                      const uint8_t* host_bytes,
                                      int64_t first_global_row, int64_t flags,
-                                     tpx_result* res) {
+                                     tpx_result* res,
+                                     tpx_table** cache_out = nullptr) {
     hipStream_t stream = nullptr;
     int dev = cur_device();
     hipEvent_t eb0, eb1;
@@ -1599,14 +1909,23 @@ static int64_t csv_boundary_and_core(tpx_stage* st, void* d_in_p, long long size
 
     PayloadSrc psrc{host_bytes, nullptr, 0};
     return run_core(st, d_in_p, d_offs, nrows, first_global_row, size, res, psrc,
-                    stream, flags, &emit_range);
+                    stream, flags, &emit_range, nullptr, cache_out);
 }
 
-extern "C" int64_t tpx_stage_execute_csv(tpx_stage* st, const uint8_t* csv_bytes,
-                                         int64_t size, int64_t first_global_row,
-                                         tpx_result* res) {
+// a failed cache execute never hands out a table
+static int64_t cache_rc(int64_t rc, tpx_table** table) {
+    if (rc != 0 && table && *table) {
+        tpx_table_free(*table);
+        *table = nullptr;
+    }
+    return rc;
+}
+
+static int64_t execute_csv_host(tpx_stage* st, const uint8_t* csv_bytes,
+                                int64_t size, int64_t first_global_row,
+                                tpx_result* res, tpx_table** cache_out) {
     memset(res, 0, sizeof(*res));
-    if (!st->loaded) { set_err("stage not loaded on a GPU"); return -1; }
+    if (!st || !st->loaded) { set_err("stage not loaded on a GPU"); return -1; }
     if (!st->k_csv_chunk || !st->k_csv_sel || !st->k_csv_rows) {
         set_err("stage compiled without csv kernels");
         return -1;
@@ -1621,6 +1940,7 @@ extern "C" int64_t tpx_stage_execute_csv(tpx_stage* st, const uint8_t* csv_bytes
     hipEventCreate(&ev0); hipEventCreate(&ev1);
     hipEventRecord(ev0, stream);
     ARENA_TAKE(d_in, (size_t)size + 80);  // mask-walk 64-B group overread slack
+    xfer_h2d((size_t)size);
     HIP_CHECK(hipMemcpyAsync(d_in, csv_bytes, (size_t)size,
                              hipMemcpyHostToDevice, stream));
     hipEventRecord(ev1, stream);
@@ -1631,7 +1951,22 @@ extern "C" int64_t tpx_stage_execute_csv(tpx_stage* st, const uint8_t* csv_bytes
     (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
 
     return csv_boundary_and_core(st, d_in, size, csv_bytes, first_global_row, 0,
-                                 res);
+                                 res, cache_out);
+}
+
+extern "C" int64_t tpx_stage_execute_csv(tpx_stage* st, const uint8_t* csv_bytes,
+                                         int64_t size, int64_t first_global_row,
+                                         tpx_result* res) {
+    return execute_csv_host(st, csv_bytes, size, first_global_row, res, nullptr);
+}
+
+extern "C" int64_t tpx_stage_cache_csv(tpx_stage* st, const uint8_t* csv_bytes,
+                                       int64_t size, int64_t first_global_row,
+                                       tpx_result* res, tpx_table** table) {
+    if (!table) { set_err("tpx_stage_cache_csv: table is NULL"); return -1; }
+    *table = nullptr;
+    return cache_rc(execute_csv_host(st, csv_bytes, size, first_global_row,
+                                     res, table), table);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1644,6 +1979,7 @@ extern "C" uint64_t tpx_dev_alloc(int64_t size) {
 }
 
 extern "C" int64_t tpx_dev_upload(uint64_t dst, const void* src, int64_t size) {
+    xfer_h2d((size_t)size);
     HIP_CHECK(hipMemcpy((void*)(uintptr_t)dst, src, (size_t)size,
                         hipMemcpyHostToDevice));
     return 0;
@@ -1665,18 +2001,36 @@ extern "C" void tpx_pinned_free(uint64_t ptr) {
     if (ptr) (void)hipHostFree((void*)(uintptr_t)ptr);
 }
 
-extern "C" int64_t tpx_stage_execute_csv_dev(tpx_stage* st, uint64_t dev_bytes,
-                                             int64_t size,
-                                             int64_t first_global_row,
-                                             int64_t flags, tpx_result* res) {
+static int64_t execute_csv_dev(tpx_stage* st, uint64_t dev_bytes, int64_t size,
+                               int64_t first_global_row, int64_t flags,
+                               tpx_result* res, tpx_table** cache_out) {
     memset(res, 0, sizeof(*res));
-    if (!st->loaded) { set_err("stage not loaded on a GPU"); return -1; }
+    if (!st || !st->loaded) { set_err("stage not loaded on a GPU"); return -1; }
     res->bytes_in = size;
     int dev = cur_device();
     g_arena[dev].begin();
     if (size == 0) { empty_result(res, st->desc.sink == "mem"); return 0; }
     return csv_boundary_and_core(st, (void*)(uintptr_t)dev_bytes, size, nullptr,
-                                 first_global_row, flags, res);
+                                 first_global_row, flags, res, cache_out);
+}
+
+extern "C" int64_t tpx_stage_execute_csv_dev(tpx_stage* st, uint64_t dev_bytes,
+                                             int64_t size,
+                                             int64_t first_global_row,
+                                             int64_t flags, tpx_result* res) {
+    return execute_csv_dev(st, dev_bytes, size, first_global_row, flags, res,
+                           nullptr);
+}
+
+extern "C" int64_t tpx_stage_cache_csv_dev(tpx_stage* st, uint64_t dev_bytes,
+                                           int64_t size,
+                                           int64_t first_global_row,
+                                           tpx_result* res,
+                                           tpx_table** table) {
+    if (!table) { set_err("tpx_stage_cache_csv_dev: table is NULL"); return -1; }
+    *table = nullptr;
+    return cache_rc(execute_csv_dev(st, dev_bytes, size, first_global_row, 0,
+                                    res, table), table);
 }
 
 extern "C" void tpx_result_free(tpx_result* res) {

@@ -548,9 +548,17 @@ def _stream_files_to_device(glib, fmeta, dev, total_len, metrics):
 # ---- main entry ------------------------------------------------------------------
 
 def run_csv(context, src, logical_ops, sink=None,
-            keep_exceptions=False) -> CollectOutcome:
+            keep_exceptions=False, device_cache=False) -> CollectOutcome:
+    """device_cache (cache() of an eligible pipeline, engine.
+    cache_eligibility): each chunk's kept rows are packed into a columnar
+    device table and stay in HBM (out.device_cache) — only their row keys
+    come back. Where the run turns out not to allow it (fallback stage,
+    nested output type, several devices, failed device allocation) the rows
+    come back as always and out.cache_reason says why."""
     opts = context.options_obj
     out = CollectOutcome()
+    if device_cache:
+        out.cache_reason = "stage fell back to the interpreter"
 
     paths = sorted(glob.glob(src.pattern)) if not os.path.isfile(src.pattern) \
         else [src.pattern]
@@ -626,6 +634,7 @@ def run_csv(context, src, logical_ops, sink=None,
         return data
 
     sp = plan.build_stage(col_types, names, logical_ops)
+    out.output_columns = sp.output_columns  # sniffed names: cache() keeps them
     sink_kind = "csv" if (sink is not None and sink[0] == "csv") else "mem"
 
     if not sp.compilable:
@@ -688,6 +697,22 @@ def run_csv(context, src, logical_ops, sink=None,
     out.metrics = {"t_h2d_ms": 0.0, "t_kernel_ms": 0.0, "t_d2h_ms": 0.0,
                    "bytes_in": 0, "bytes_out": 0, "chunks": len(chunks) - 1}
     nch = len(chunks) - 1
+    # device cache: decided here for what only the run knows; dcache["on"]
+    # drops to False if a table cannot be allocated (rows then come back to
+    # the host for that chunk, and the tables made so far are downloaded)
+    dcache = {"on": False}
+    if device_cache:
+        from .engine import DeviceTable, cache_eligibility
+        where, why = cache_eligibility(opts, src, logical_ops,
+                                       sp.gpu_output_types)
+        if where == "device" and (sink_kind != "mem" or not keep_exceptions):
+            where, why = "host", "not a mem-sink cache run"
+        if where == "device" and (world > 1 or min(want or ndev, ndev) > 1):
+            where, why = "host", "multi-device fan-out"
+        dcache["on"] = where == "device"
+        out.cache_reason = why
+        out.metrics["t_pack_ms"] = 0.0
+    chunk_tabs = [None] * nch     # device cache: DeviceTable per chunk
     my_work = [ci for ci in range(nch) if ci % world == rank]
     # per-chunk result slots, merged in chunk order below
     chunk_rows = [None] * nch     # mem sink: list[(key,row)]
@@ -708,12 +733,34 @@ def run_csv(context, src, logical_ops, sink=None,
         base = ci << _CHUNK_SHIFT  # composite ordering key namespace
         clen = chunks[ci + 1] - chunks[ci]
         res = TpxResult()
-        if resident_dev:
+        cptr = None
+        if not resident_dev:
+            cptr = ctypes.cast(data_arr.ctypes.data + chunks[ci],
+                               ctypes.POINTER(ctypes.c_uint8))
+        tab = ctypes.c_void_p()
+        packed = False
+        if dcache["on"]:
+            if resident_dev:
+                rc = glib.lib.tpx_stage_cache_csv_dev(
+                    stage_h, resident_dev, clen, base, ctypes.byref(res),
+                    ctypes.byref(tab))
+            else:
+                rc = glib.lib.tpx_stage_cache_csv(
+                    stage_h, cptr, clen, base, ctypes.byref(res),
+                    ctypes.byref(tab))
+            if rc == 2:  # TPX_E_TABLE_ALLOC: no table — today's host cache
+                dcache["on"] = False
+                out.cache_reason = "device allocation failed: " + glib.err()
+                glib.lib.tpx_result_free(ctypes.byref(res))
+                res = TpxResult()
+            else:
+                packed = True
+        if packed:
+            pass
+        elif resident_dev:
             rc = glib.lib.tpx_stage_execute_csv_dev(
                 stage_h, resident_dev, clen, base, 0, ctypes.byref(res))
         else:
-            cptr = ctypes.cast(data_arr.ctypes.data + chunks[ci],
-                               ctypes.POINTER(ctypes.c_uint8))
             rc = glib.lib.tpx_stage_execute_csv(
                 stage_h, cptr, clen, base, ctypes.byref(res))
         if rc != 0:
@@ -774,7 +821,18 @@ def run_csv(context, src, logical_ops, sink=None,
                 chunk_pend[ci] = pend
             chunk_repl[ci] = repl
             chunk_excs[ci] = excs
-            if sink_kind == "mem":
+            if packed:
+                # the rows stayed in HBM; only their keys came back
+                n_out = res.out_num_rows
+                keys = _np.ctypeslib.as_array(
+                    res.out_row_indices, shape=(n_out,)).copy() \
+                    if n_out else _np.empty(0, _np.int64)
+                with mlock:
+                    out.metrics["t_pack_ms"] += res.t_write_ms
+                if tab.value:
+                    chunk_tabs[ci] = DeviceTable(glib, tab.value, keys,
+                                                 sp.gpu_output_types)
+            elif sink_kind == "mem":
                 out_bytes = ctypes.string_at(res.out_data, res.out_size)
                 _offs = (_np.ctypeslib.as_array(
                     res.out_row_offsets,
@@ -831,6 +889,18 @@ def run_csv(context, src, logical_ops, sink=None,
         out.metrics["devices"] = use_devs
     # pools persist across executions (presolve._POOLS; atexit shutdown)
 
+    if device_cache and not dcache["on"]:
+        # a table could not be allocated part-way: the tables made before it
+        # come back to the host, so the outcome is today's host cache
+        for ci, t in enumerate(chunk_tabs):
+            if t is not None:
+                rws = t.host_rows()
+                if len(t.col_types) == 1:
+                    rws = [(v,) for v in rws]
+                chunk_rows[ci] = list(zip(t.keys.tolist(), rws))
+                t.free()
+                chunk_tabs[ci] = None
+
     replayed = {}
     all_rows = []
     text_parts = []
@@ -863,6 +933,18 @@ def run_csv(context, src, logical_ops, sink=None,
             return replay_csv_row(payload, _ct, _nv, ops, _nm, _dl,
                                   used=used2)
         out.pending_replayer = _csv_replayer
+
+    if dcache["on"]:
+        out.device_cache = {
+            "tables": [t for t in chunk_tabs if t is not None],
+            "extras": sorted(((k, v) for k, lst in replayed.items()
+                              for v in lst), key=lambda t: t[0]),
+            "types": list(sp.gpu_output_types),
+            "device": int(opts.get("tuplex.gpu.device", "0")),
+        }
+        out.cache_reason = None
+        out.rows = []
+        return out
 
     if dist and world > 1:
         out.metrics["world"] = world

@@ -110,17 +110,39 @@ class DataSet:
         the reference's deferred resolution. Pipelines ending in
         aggregate/unique consume row identity, so those cache the final
         values (nothing left to resolve into)."""
-        from .context import CachedSource, ParallelizeSource
+        from . import engine
+        from .context import (CachedSource, DeviceCachedSource,
+                              ParallelizeSource)
         has_agg = any(op[0] in ("aggregate", "aggregateByKey", "unique")
                       for op in self._ops)
-        outcome = self._context._execute(self, keep_exceptions=not has_agg)
-        if (has_agg or outcome.row_keys is None
+        # compiled csv/text pipelines keep their rows in HBM as columnar
+        # device partitions (tuplex.gpu.deviceCache; DESIGN.md §8f-4);
+        # metrics["cache"] says where the rows went, cache_reason why not
+        where, reason = engine.cache_eligibility(
+            self._context.options_obj, self._source, self._ops)
+        outcome = self._context._execute(self, keep_exceptions=not has_agg,
+                                         device_cache=(where == "device"))
+        dc = outcome.device_cache
+        outcome.metrics["cache"] = "device" if dc is not None else "host"
+        if dc is None:
+            outcome.metrics["cache_reason"] = (
+                reason or outcome.cache_reason or "not a compiled GPU stage")
+        # a csv source finds its column names itself (header); keep them
+        cols = self.columns
+        if cols is None and not has_agg:
+            cols = outcome.output_columns
+        if dc is not None:
+            src = DeviceCachedSource(dc["tables"], dc["extras"], dc["types"],
+                                     dc["device"], outcome.pending,
+                                     outcome.pending_replayer,
+                                     list(self._ops), cols)
+        elif (has_agg or outcome.row_keys is None
                 or outcome.pending_replayer is None):
             src = ParallelizeSource(list(outcome.rows), self.columns)
         else:
             src = CachedSource(list(outcome.rows), outcome.row_keys,
                                outcome.pending, outcome.pending_replayer,
-                               list(self._ops), self.columns)
+                               list(self._ops), cols)
         ds = DataSet(self._context, src)
         ds._last_outcome = outcome
         return ds

@@ -106,6 +106,34 @@ class GpuLib:
                                                   ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int64,
                                                   ctypes.POINTER(TpxResult)]
+        # device-resident cache() partitions (tpx_table) + transfer counters
+        for name in ("tpx_stage_cache_csv", "tpx_stage_cache_csv_dev"):
+            getattr(lib, name).restype = ctypes.c_int64
+        lib.tpx_stage_cache_csv.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64,
+            ctypes.c_int64, ctypes.POINTER(TpxResult),
+            ctypes.POINTER(ctypes.c_void_p)]
+        lib.tpx_stage_cache_csv_dev.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64,
+            ctypes.POINTER(TpxResult), ctypes.POINTER(ctypes.c_void_p)]
+        lib.tpx_table_rows.restype = ctypes.c_int64
+        lib.tpx_table_rows.argtypes = [ctypes.c_void_p]
+        lib.tpx_table_bytes.restype = ctypes.c_int64
+        lib.tpx_table_bytes.argtypes = [ctypes.c_void_p]
+        lib.tpx_table_slots.restype = ctypes.c_int64
+        lib.tpx_table_slots.argtypes = [ctypes.c_void_p,
+                                        ctypes.POINTER(ctypes.c_void_p),
+                                        ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.c_int64]
+        lib.tpx_table_download.restype = ctypes.c_int64
+        lib.tpx_table_download.argtypes = [ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_void_p),
+                                           ctypes.c_int64]
+        lib.tpx_table_free.restype = None
+        lib.tpx_table_free.argtypes = [ctypes.c_void_p]
+        lib.tpx_xfer_stats.restype = ctypes.c_int64
+        lib.tpx_xfer_stats.argtypes = [ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(ctypes.c_int64)]
         self.lib = lib
         os.makedirs(_CACHE_DIR, exist_ok=True)
         self._stage_cache = {}
@@ -121,6 +149,12 @@ class GpuLib:
 
     def err(self) -> str:
         return self.lib.tpx_last_error().decode("utf-8", "replace")
+
+    def xfer_stats(self):
+        """(h2d_bytes, d2h_bytes) the library has copied so far, cumulative."""
+        h, d = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.lib.tpx_xfer_stats(ctypes.byref(h), ctypes.byref(d))
+        return h.value, d.value
 
     def compile_stage(self, src: str, desc: str, compile_only=False):
         key = (src, compile_only)
@@ -237,8 +271,13 @@ def execute_stage_col(sp: plan.StageProgram, dev_slots, n_rows: int,
     stage = glib.compile_stage(src, desc)
     arr = (ctypes.c_void_p * len(dev_slots))(
         *[ctypes.c_void_p(p or 0) for p in dev_slots])
+    return _run_col(glib, stage, sp, arr, len(dev_slots), n_rows, in_bytes)
+
+
+def _run_col(glib, stage, sp, arr, n_slots, n_rows, in_bytes) -> ExecResult:
+    """One tpx_stage_execute_col call over a device slot table, decoded."""
     res = TpxResult()
-    rc = glib.lib.tpx_stage_execute_col(stage, arr, len(dev_slots), n_rows,
+    rc = glib.lib.tpx_stage_execute_col(stage, arr, n_slots, n_rows,
                                         in_bytes, 0, 0, ctypes.byref(res))
     if rc != 0:
         raise RuntimeError("columnar stage execute failed: " + glib.err())
@@ -262,12 +301,137 @@ def execute_stage_col(sp: plan.StageProgram, dev_slots, n_rows: int,
                 out.exceptions.append((row, ecode, opid))
         out.metrics = {
             "t_h2d_ms": res.t_h2d_ms, "t_kernel_ms": res.t_kernel_ms,
-            "t_d2h_ms": res.t_d2h_ms,
+            "t_d2h_ms": res.t_d2h_ms, "t_main_ms": res.t_main_ms,
             "bytes_in": res.bytes_in, "bytes_out": res.bytes_out,
         }
         return out
     finally:
         glib.lib.tpx_result_free(ctypes.byref(res))
+
+
+# ---- device-resident cache() partitions -------------------------------------------
+
+_CACHE_BASES = (T.I64, T.F64, T.BOOL, T.STR)
+
+
+def cache_eligibility(options, source, ops, output_types=None):
+    """Where cache() of the pipeline (source, ops) keeps its rows:
+    ("device", None), or ("host", reason). Pure bookkeeping — it never opens
+    the GPU library. output_types, once the plan knows them, must all be
+    i64 / f64 / bool / str or an Option of those. What only the run itself
+    can tell (a stage that does not compile, visible devices, a failed device
+    allocation) is decided there and reported the same way."""
+    if not options.get_bool("tuplex.gpu.deviceCache"):
+        return "host", "tuplex.gpu.deviceCache is off"
+    kind = getattr(source, "kind", None)
+    if kind != "csv":
+        return "host", {"mem": "parallelize source",
+                        "orc": "orc source",
+                        "cached": "cached source",
+                        "dcached": "cached source"}.get(kind, "unknown source")
+    if any(op[0] in _AGG_KINDS for op in ops):
+        return "host", "trailing aggregate or unique"
+    if any(op[0] == "join" and _dup_join(op) for op in ops):
+        return "host", "duplicate-key join"
+    from . import csvio
+    dist = csvio._dist()
+    if dist is not None and dist.get_world_size() > 1:
+        return "host", "multi-process run"
+    if int(options.get("tuplex.gpu.devices", "1") or "0") > 1:
+        return "host", "multi-device fan-out"
+    if output_types is not None:
+        for t in output_types:
+            if T.deopt(t) not in _CACHE_BASES:
+                return "host", "nested output type"
+    return "device", None
+
+
+def _dup_join(op):
+    """A join op whose build side repeats a key (1:N expansion)."""
+    _, rrows, rcols, _lk, rk = op[:5]
+    try:
+        ki = rcols.index(rk)
+        keys = [r[ki] for r in rrows]
+    except Exception:  # noqa: BLE001 - malformed join: build_stage reports it
+        return True
+    return len(set(keys)) != len(keys)
+
+
+class DeviceTable:
+    """One tpx_table: a dense columnar partition in HBM, owned by the library
+    and freed with this object. keys[i] is the ordered-merge key of row i."""
+
+    def __init__(self, glib, handle, keys, col_types):
+        self._glib = glib
+        self.handle = handle
+        self.keys = keys
+        self.col_types = list(col_types)
+        self.rows = int(glib.lib.tpx_table_rows(handle))
+        self.bytes = int(glib.lib.tpx_table_bytes(handle))
+        self._host = None
+
+    def slots(self):
+        n = 3 * len(self.col_types)
+        arr = (ctypes.c_void_p * n)()
+        nbytes = (ctypes.c_int64 * n)()
+        if self._glib.lib.tpx_table_slots(self.handle, arr, nbytes, n) != n:
+            raise RuntimeError("tpx_table_slots: " + self._glib.err())
+        return arr, list(nbytes)
+
+    def host_rows(self):
+        """Rows of the partition as python values, from a lazily downloaded
+        host copy (kept afterwards)."""
+        if self._host is None:
+            import numpy as np
+            _arr, nbytes = self.slots()
+            bufs = [np.empty(b, dtype=np.uint8) if b else None for b in nbytes]
+            ptrs = (ctypes.c_void_p * len(bufs))(
+                *[ctypes.c_void_p(b.ctypes.data if b is not None else 0)
+                  for b in bufs])
+            if self._glib.lib.tpx_table_download(self.handle, ptrs,
+                                                 len(bufs)) != 0:
+                raise RuntimeError("tpx_table_download: " + self._glib.err())
+            self._host = decode_table(bufs, self.col_types, self.rows)
+        return self._host
+
+    def free(self):
+        if self.handle:
+            self._glib.lib.tpx_table_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def decode_table(bufs, col_types, m):
+    """Rows of a downloaded partition: bufs holds 3 uint8 arrays (or None) per
+    column in the columnar-source slot layout. One column -> scalar rows."""
+    import numpy as np
+    cols = []
+    for k, t in enumerate(col_types):
+        base = T.deopt(t)
+        b0, b1, b2 = bufs[3 * k], bufs[3 * k + 1], bufs[3 * k + 2]
+        if base == T.STR:
+            offs = b0.view(np.int64)[:m + 1].tolist()
+            data = b1.tobytes() if b1 is not None else b""
+            vals = [data[offs[i]:offs[i + 1]].decode("utf-8")
+                    for i in range(m)]
+        elif base == T.I64:
+            vals = b0.view(np.int64)[:m].tolist() if m else []
+        elif base == T.F64:
+            vals = b0.view(np.float64)[:m].tolist() if m else []
+        else:
+            vals = (b0[:m] != 0).tolist() if m else []
+        if T.is_opt(t) and m:
+            nul = b2[:m] != 0
+            vals = [None if z else v for v, z in zip(vals, nul.tolist())]
+        cols.append(vals)
+    if len(cols) == 1:
+        return cols[0]
+    return list(zip(*cols))
 
 
 def run_collect(data: List[Any], logical_ops: List[tuple],
@@ -489,6 +653,137 @@ def run_cached(context, src, post_ops, keep_exceptions=False):
     return out
 
 
+def _count_exc(counts, e):
+    nm = type(e).__name__
+    counts[nm] = counts.get(nm, 0) + 1
+
+
+def run_dcached(context, src, post_ops, keep_exceptions=False):
+    """Downstream ops over a DEVICE-resident cache (context.
+    DeviceCachedSource): every table runs through the columnar source
+    (tpx_stage_execute_col) where it lies, keyed by the partition's host row
+    keys; host extras run through run_collect, stored exceptions through the
+    replayer with the full chain, and all of it merges by key as in
+    run_cached. GPU-reducible aggregates fold one partial per table. Rows the
+    second stage diverts are fetched from a lazily downloaded host copy of
+    their partition. What the columnar path does not cover — no ops at all,
+    a stage that does not compile, a further cache() — materialises the
+    tables to a host CachedSource and takes run_cached."""
+    lead = 0
+    while lead < len(post_ops) and post_ops[lead][0] in ("resolve", "ignore"):
+        lead += 1
+    ops2 = list(post_ops[lead:])
+    row_run_ops = [op for op in ops2 if op[0] not in _AGG_KINDS]
+    names = src.columns
+    types = list(src.col_types)
+    sp = None
+    if ops2 and not keep_exceptions and \
+            plan.find_dup_join_split(ops2) is None:
+        sp = plan.build_stage(types, names, ops2)
+        if sp.compilable:
+            try:
+                csrc, desc = codegen.generate_stage(sp, source="col",
+                                                    sink="mem")
+            except codegen.CodegenError:
+                sp = None
+        else:
+            sp = None
+    if sp is None:
+        return run_cached(context, src.host_source(), post_ops,
+                          keep_exceptions=keep_exceptions)
+
+    glib = GpuLib.get()
+    glib.lib.tpx_set_device(src.device)
+    stage = glib.compile_stage(csrc, desc)
+    scalar_input = len(types) == 1
+    out = CollectOutcome()
+    out.mode = "gpu"
+    out.metrics = {"t_h2d_ms": 0.0, "t_kernel_ms": 0.0, "t_d2h_ms": 0.0,
+                   "t_main_ms": 0.0, "bytes_in": 0, "bytes_out": 0,
+                   "partitions": len(src.tables)}
+    gpu_pairs = []   # (key, gpu output row tuple)
+    host_pairs = []  # (key, row value) — rows that ran on the interpreter
+
+    def take(key, r):
+        if r[0] == "row":
+            host_pairs.append((key, r[1]))
+        elif r[0] == "exc":
+            _count_exc(out.exception_counts, r[1])
+        elif r[0] == "rows":
+            for v in r[1]:
+                host_pairs.append((key, v))
+            for e in r[2]:
+                _count_exc(out.exception_counts, e)
+
+    for tab in src.tables:
+        if not tab.rows:
+            continue
+        arr, _nb = tab.slots()
+        er = _run_col(glib, stage, sp, arr, len(arr), tab.rows, tab.bytes)
+        for k, v in er.metrics.items():
+            out.metrics[k] += v
+        keys = tab.keys
+        if sp.agg_expr is not None:
+            gpu_pairs.extend((0, row) for row in er.rows)
+        else:
+            gpu_pairs.extend((int(keys[i]), row)
+                             for row, i in zip(er.rows, er.row_indices))
+        if er.exceptions:
+            rows = tab.host_rows()  # the columnar source carries no payload
+            for (i, _ec, _opid) in sorted(er.exceptions):
+                take(int(keys[i]), resolve.replay_row(rows[i], ops2, names,
+                                                      scalar_input))
+    if src.extras:
+        if row_run_ops:
+            o2 = run_collect([v for _, v in src.extras], row_run_ops, names,
+                             context.options_obj, keep_keys=True)
+            for nm, c in o2.exception_counts.items():
+                out.exception_counts[nm] = out.exception_counts.get(nm, 0) + c
+            for k2, row in zip(o2.row_keys, o2.rows):
+                host_pairs.append((src.extras[k2][0], row))
+        else:
+            host_pairs.extend(src.extras)
+    full_ops = list(src.pre_ops) + list(post_ops)
+    for key, payload in src.pending:
+        take(key, src.replayer(payload, full_ops))
+
+    agg_cols = sp.output_columns
+    if sp.agg_expr is not None:
+        host_rows = [v for _, v in sorted(host_pairs, key=lambda t: t[0])]
+        if sp.agg_unique and sp.agg_key_idx is not None:
+            keys = dict.fromkeys(row[0] for _, row in gpu_pairs)
+            for v in host_rows:
+                keys[v if not isinstance(v, tuple) else v[0]] = None
+            out.rows = list(keys)
+        elif sp.agg_key_idx is not None:
+            _opid, _comb, agg_fn, initial, key_cols = sp.aggregate
+            table = {}
+            for _, row in gpu_pairs:  # per-table partials: + initial once
+                table[row[0]] = table.get(row[0], initial) + row[1]
+            ki = agg_cols.index(key_cols[0])
+            for v in host_rows:
+                rt = v if isinstance(v, tuple) else (v,)
+                table[rt[ki]] = agg_fn(table.get(rt[ki], initial),
+                                       _agg_row(v, agg_cols))
+            out.rows = [(k, v) for k, v in table.items()]
+        else:
+            _opid, _comb, agg_fn, initial = sp.aggregate
+            acc = initial
+            for _, row in gpu_pairs:
+                acc = acc + row[0]
+            for v in host_rows:
+                acc = agg_fn(acc, _agg_row(v, agg_cols))
+            out.rows = [acc]
+        return out
+
+    pairs = gpu_pairs + host_pairs
+    pairs.sort(key=lambda t: t[0])
+    merged = [_unwrap_row(v) if isinstance(v, tuple) else v for _, v in pairs]
+    out.rows = finalize_merged(merged, post_ops,
+                               output_columns_of(names, post_ops))
+    return out
+
+
 def finalize_merged(merged, logical_ops, output_columns):
     """Host-side finalization of trailing unique/aggregate/aggregateByKey over
     interpreter-merged rows (fallback paths and non-GPU-reducible aggregates).
@@ -558,3 +853,11 @@ class CollectOutcome:
         self.pending = []
         self.pending_replayer = None
         self.row_keys = None
+        # device cache (csvio.run_csv with device_cache=True): the kept rows
+        # stayed in HBM — {"tables": [DeviceTable], "extras": [(key, row)],
+        # "types", "device"}; cache_reason says why they did not
+        self.device_cache = None
+        self.cache_reason = None
+        # column names of the output where the source found them itself
+        # (csv header); None = the DataSet's own bookkeeping holds
+        self.output_columns = None

@@ -57,6 +57,7 @@ DEFAULTS = {
     "tuplex.gpu.heapFactor": "2.0",
     "tuplex.gpu.devices": "1",            # in-process device fan-out (N>1 opt-in; 0 = all visible)
     "tuplex.gpu.resolveProcesses": "0",   # parallel host resolver width (0 = auto, 1 = inline)
+    "tuplex.gpu.deviceCache": "true",     # cache() keeps columnar partitions in HBM where it can
 }
 
 
