@@ -221,6 +221,46 @@ int64_t tpx_table_download(const tpx_table* table, void* const* host_slots,
 
 void tpx_table_free(tpx_table* table);
 
+/* ---- device join tables ----------------------------------------------------------
+ * A tpx_jtable is the build side of a unique-key hash join kept in HBM: the
+ * build columns as Arrow-layout arrays plus a slot table built over them by
+ * the stage module's build kernel (csrc/tpx_join.hip.h). Like a tpx_table it
+ * owns its memory (hipMalloc, not workspace-arena memory), lives on the
+ * device that was current when it was made and honours TPX_TABLE_MAX_BYTES.
+ * A stage whose generated source declares `tpx_jt[]` probes the table that
+ * was last bound to the entry; stage handles are shared between pipelines
+ * with the same source, so a caller binds immediately before each run. */
+typedef struct tpx_jtable tpx_jtable;
+
+/* Upload n_cols build columns of n_rows rows and build the slot table over
+ * column key_col (int64 keys, or strings if key_is_str). host_slots holds 3
+ * HOST pointers per column in the tpx_stage_execute_col slot layout (values
+ * or int64 offsets [n_rows+1] | string bytes | uint8 null mask) and
+ * slot_bytes the bytes behind each; a NULL pointer means the slot is absent,
+ * a non-NULL one with 0 bytes a present, empty array. Keys must be unique
+ * and non-null; at most 64 columns and 2^30 rows. `stage` must be a loaded
+ * stage whose source includes the join header. Complete (synchronised) on
+ * return. Returns 0; TPX_E_TABLE_ALLOC (and no table, never a partial one)
+ * when the memory cannot be had; -1 on any other error. n_rows == 0 gives a
+ * valid table on which every probe misses. */
+int64_t tpx_jtable_build(tpx_stage* stage, void* const* host_slots,
+                         const int64_t* slot_bytes, int64_t n_cols,
+                         int64_t n_rows, int64_t key_col, int64_t key_is_str,
+                         tpx_jtable** out);
+
+/* Make `table` the one the stage's join_index-th device join probes, for
+ * every execute entry point, until the next bind of that entry. */
+int64_t tpx_stage_bind_jtable(tpx_stage* stage, int64_t join_index,
+                              const tpx_jtable* table);
+
+/* Build rows / device bytes (-1 for NULL); HIP-event time of the build
+ * kernel in ms (0 for an empty build side, -1 for NULL). */
+int64_t tpx_jtable_rows(const tpx_jtable* table);
+int64_t tpx_jtable_bytes(const tpx_jtable* table);
+double  tpx_jtable_build_ms(const tpx_jtable* table);
+
+void tpx_jtable_free(tpx_jtable* table);
+
 /* Cumulative per-process byte counts of the host<->device copies the library
  * has issued (device-to-device copies count as neither). Either pointer may
  * be NULL. Works without a GPU. Returns 0. */

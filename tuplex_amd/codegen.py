@@ -79,6 +79,18 @@ def ci_header() -> str:
     return _CI_HEADER_CACHE
 
 
+_JOIN_HEADER_CACHE = None
+
+
+def join_header() -> str:
+    global _JOIN_HEADER_CACHE
+    if _JOIN_HEADER_CACHE is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                            "csrc", "tpx_join.hip.h")
+        _JOIN_HEADER_CACHE = open(path).read()
+    return _JOIN_HEADER_CACHE
+
+
 def _ctype(t):
     base = T.deopt(t)
     if base in (T.I64,):
@@ -477,6 +489,8 @@ class StageCodegen:
         """Probe an embedded build table; extend the row context with the
         right columns (JoinOperator.cc:164 layout)."""
         rrows, rcols, lki, rki, how = op.join
+        if getattr(op, "join_dev", None) is not None:
+            return self._emit_join_device(em, op, rc)
         nm, tsize, str_key, out_info, dup = self._emit_join_table(op)
         kv, _kt, knv = rc[lki]
         ji = em.fresh("ji")
@@ -541,6 +555,73 @@ class StageCodegen:
                 t = T.I64
             new_rc.append((v, ("opt", t) if nullable else t, nv))
         return new_rc
+
+    def _emit_join_device(self, em, op, rc):
+        """Probe a device join table (csrc/tpx_join.hip.h): tpx_jt[i] is
+        filled by the library before a run, so the text below depends on the
+        build side's schema only — key kind, column kinds, which columns can
+        be null. The rc entries are those of the embedded probe."""
+        _rrows, _rcols, lki, _rki, how = op.join
+        jd = op.join_dev
+        self.uses_jt = True
+        jt = "tpx_jt[%d]" % jd["index"]
+        kv, _kt, knv = rc[lki]
+        ji = em.fresh("ji")
+        probe = ("tpx_join_probe_str(%s, %s)" if jd["key_str"]
+                 else "tpx_join_probe_i64(%s, %s)") % (jt, kv)
+        if knv:
+            em.w("int %s = -1;" % ji)
+            em.w("if (!(%s)) %s = %s;" % (knv, ji, probe))
+        else:
+            em.w("int %s = %s;" % (ji, probe))
+        if how == "inner":
+            em.w("if (%s < 0) { o.keep = false; return 0; }" % ji)
+        new_rc = [rc[i2] for i2 in range(len(rc)) if i2 != lki] + [rc[lki]]
+        left_join = how == "left"
+        sel = em.fresh("jr")
+        em.w("long long %s = %s < 0 ? 0 : %s;" % (sel, ji, ji))
+        for j, kindc, has_null in jd["cols"]:
+            nullable = left_join or has_null
+            nv = None
+            if nullable:
+                nv = em.fresh("jn")
+                if has_null:
+                    em.w("bool %s = %s < 0 || ((const unsigned char*)"
+                         "%s.cols[%d])[%s];" % (nv, ji, jt, 3 * j + 2, sel))
+                else:
+                    em.w("bool %s = %s < 0;" % (nv, ji))
+            v = em.fresh("jv")
+            if kindc == "str":
+                o = em.fresh("jo")
+                em.w("const long long* %s = (const long long*)%s.cols[%d] + %s;"
+                     % (o, jt, 3 * j, sel))
+                em.w("tstr %s = {(const char*)%s.cols[%d] + %s[0], "
+                     "%s[1] - %s[0]};" % (v, jt, 3 * j + 1, o, o, o))
+                t = T.STR
+            elif kindc == "f64":
+                em.w("double %s = ((const double*)%s.cols[%d])[%s];"
+                     % (v, jt, 3 * j, sel))
+                t = T.F64
+            elif kindc == "bool":
+                em.w("bool %s = ((const unsigned char*)%s.cols[%d])[%s] != 0;"
+                     % (v, jt, 3 * j, sel))
+                t = T.BOOL
+            else:
+                em.w("long long %s = ((const long long*)%s.cols[%d])[%s];"
+                     % (v, jt, 3 * j, sel))
+                t = T.I64
+            new_rc.append((v, ("opt", t) if nullable else t, nv))
+        return new_rc
+
+    def _jt_section(self):
+        """Device join table header + the table descriptors the library
+        binds — only for stages with a device join (same reasoning as
+        _re_section)."""
+        nj = len(getattr(self.sp, "device_joins", None) or [])
+        if not nj or not getattr(self, "uses_jt", False):
+            return []
+        return [join_header(), "",
+                "__device__ TpxJoinTab tpx_jt[%d];" % nj, ""]
 
     def _peephole(self, em, n, rc, opid):
         """Pattern rewrites that must run BEFORE strict arg evaluation.
@@ -1557,6 +1638,7 @@ class StageCodegen:
             runtime_header(),
             "",
         ] + self._ci_section() + self._re_section() + self._fmt_section() + \
+            self._jt_section() + \
             self.lit_defs + \
             self.join_defs + [
             "",

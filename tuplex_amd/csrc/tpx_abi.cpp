@@ -576,6 +576,15 @@ extern "C" int64_t tpx_table_download(const tpx_table* t,
     return 0;
 }
 
+// byte cap of one table (TPX_TABLE_MAX_BYTES, read once); -1 = none
+static long long table_env_cap() {
+    static long long cap = [] {
+        const char* e = getenv("TPX_TABLE_MAX_BYTES");
+        return e ? atoll(e) : -1LL;
+    }();
+    return cap;
+}
+
 // descriptor of tpx_cache_pack_fixed (csrc/tpx_cache.hip.h: tpx_cp_desc)
 struct CpDesc {
     const void* src;
@@ -599,10 +608,7 @@ static int64_t pack_table(tpx_stage* st, hipStream_t stream, int dev,
         set_err("stage compiled without the cache pack kernels");
         return -1;
     }
-    static long long env_cap = [] {
-        const char* e = getenv("TPX_TABLE_MAX_BYTES");
-        return e ? atoll(e) : -1LL;
-    }();
+    const long long env_cap = table_env_cap();
     int nout = (int)D.out_cols.size();
     // every array starts 256-aligned and has 128 B of slack behind it (the
     // columnar loader's string reads may run a word past a cell)
@@ -733,6 +739,193 @@ static int64_t pack_table(tpx_stage* st, hipStream_t stream, int dev,
     guard.t = nullptr;
     *d_rowkey_out = d_rowkey;
     *out = T.release();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// device join tables (tpx_jtable): the build side of a unique-key hash join as
+// Arrow-layout columns in HBM plus a slot table built on the device
+// (csrc/tpx_join.hip.h)
+
+#define TPX_JOIN_MAX_COLS 64
+
+// host mirror of TpxJoinTab (csrc/tpx_join.hip.h) — same layout
+struct JoinTabDesc {
+    void* slots;
+    unsigned long long mask;
+    long long n_rows;
+    int n_cols;
+    int key_col;
+    const void* cols[3 * TPX_JOIN_MAX_COLS];
+};
+
+struct tpx_jtable {
+    int dev = 0;
+    size_t bytes = 0;
+    double build_ms = 0.0;
+    void* block = nullptr;   // slot table + every column, one allocation
+    JoinTabDesc desc;
+};
+
+extern "C" void tpx_jtable_free(tpx_jtable* t) {
+    if (!t) return;
+    {
+        DeviceScope ds(t->dev);
+        if (t->block) (void)hipFree(t->block);
+    }
+    delete t;
+}
+
+extern "C" int64_t tpx_jtable_rows(const tpx_jtable* t) {
+    return t ? t->desc.n_rows : -1;
+}
+
+extern "C" int64_t tpx_jtable_bytes(const tpx_jtable* t) {
+    return t ? (int64_t)t->bytes : -1;
+}
+
+extern "C" double tpx_jtable_build_ms(const tpx_jtable* t) {
+    return t ? t->build_ms : -1.0;
+}
+
+extern "C" int64_t tpx_jtable_build(tpx_stage* st, void* const* host_slots,
+                                    const int64_t* slot_bytes, int64_t n_cols,
+                                    int64_t n_rows, int64_t key_col,
+                                    int64_t key_is_str, tpx_jtable** out) {
+    if (out) *out = nullptr;
+    if (!st || !st->loaded || !host_slots || !slot_bytes || !out ||
+        n_cols < 1 || n_cols > TPX_JOIN_MAX_COLS || key_col < 0 ||
+        key_col >= n_cols || n_rows < 0 || n_rows > (1LL << 30)) {
+        set_err("tpx_jtable_build: bad arguments or stage not loaded");
+        return -1;
+    }
+    hipFunction_t k_build = nullptr;
+    if (hipModuleGetFunction(&k_build, st->module,
+                             key_is_str ? "tpx_join_build_str"
+                                        : "tpx_join_build_i64") != hipSuccess) {
+        set_err("stage compiled without the join build kernels");
+        return -1;
+    }
+    const void* kslot0 = host_slots[key_col * 3];
+    const void* kslot1 = host_slots[key_col * 3 + 1];
+    if (!kslot0 || (key_is_str && !kslot1) ||
+        slot_bytes[key_col * 3] <
+            (key_is_str ? (n_rows + 1) * 8 : n_rows * 8)) {
+        set_err("tpx_jtable_build: key column missing or too short");
+        return -1;
+    }
+    unsigned long long tsize = 8;
+    while (tsize < 2ULL * (unsigned long long)(n_rows > 0 ? n_rows : 1))
+        tsize <<= 1;
+    // every array starts 256-aligned with 128 B of slack behind it (as in
+    // pack_table); the block is zeroed, so a present column of an empty
+    // build side still reads as zeros at row 0
+    auto padded = [](size_t b) { return (b + 128 + 255) & ~(size_t)255; };
+    size_t slot_sz = key_is_str ? 8 : 16;
+    size_t total = padded((size_t)tsize * slot_sz);
+    std::vector<size_t> off((size_t)n_cols * 3, 0);
+    for (int64_t k = 0; k < n_cols * 3; ++k) {
+        if (!host_slots[k]) continue;
+        if (slot_bytes[k] < 0) {
+            set_err("tpx_jtable_build: negative slot size");
+            return -1;
+        }
+        off[(size_t)k] = total;
+        total += padded((size_t)slot_bytes[k]);
+    }
+    long long cap = table_env_cap();
+    if (cap >= 0 && (long long)total > cap) {
+        set_err("join table exceeds TPX_TABLE_MAX_BYTES");
+        return TPX_E_TABLE_ALLOC;
+    }
+    std::unique_ptr<tpx_jtable> T(new tpx_jtable());
+    T->dev = cur_device();
+    if (hipMalloc(&T->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err("join table hipMalloc failed");
+        return TPX_E_TABLE_ALLOC;
+    }
+    struct Guard {
+        tpx_jtable* t;
+        ~Guard() { if (t && t->block) { (void)hipFree(t->block); t->block = nullptr; } }
+    } guard{T.get()};
+    char* base = (char*)T->block;
+    HIP_CHECK(hipMemset(base, 0, total));
+    HIP_CHECK(hipMemset(base, 0xFF, (size_t)tsize * slot_sz));
+    memset(&T->desc, 0, sizeof T->desc);
+    T->desc.slots = base;
+    T->desc.mask = tsize - 1;
+    T->desc.n_rows = n_rows;
+    T->desc.n_cols = (int)n_cols;
+    T->desc.key_col = (int)key_col;
+    for (int64_t k = 0; k < n_cols * 3; ++k) {
+        if (!host_slots[k]) continue;
+        T->desc.cols[k] = base + off[(size_t)k];
+        if (!slot_bytes[k]) continue;
+        xfer_h2d((size_t)slot_bytes[k]);
+        HIP_CHECK(hipMemcpy(base + off[(size_t)k], host_slots[k],
+                            (size_t)slot_bytes[k], hipMemcpyHostToDevice));
+    }
+    if (n_rows > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        unsigned grid = (unsigned)std::min<long long>((n_rows + 255) / 256, 8192);
+        void* slots = base;
+        unsigned long long mask = tsize - 1;
+        long long n = n_rows;
+        void* c0 = (void*)T->desc.cols[key_col * 3];
+        void* c1 = (void*)T->desc.cols[key_col * 3 + 1];
+        int rc;
+        (void)hipEventRecord(e0, nullptr);
+        if (key_is_str) {
+            void* args[] = {&c0, &c1, &n, &slots, &mask};
+            rc = launch(k_build, grid, 256, nullptr, args);
+        } else {
+            void* args[] = {&c0, &n, &slots, &mask};
+            rc = launch(k_build, grid, 256, nullptr, args);
+        }
+        (void)hipEventRecord(e1, nullptr);
+        hipError_t se = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (!rc && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return -1;
+        if (se != hipSuccess) { set_err(hipGetErrorString(se)); return -1; }
+        T->build_ms = ms;
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    T->bytes = total;
+    guard.t = nullptr;
+    *out = T.release();
+    return 0;
+}
+
+extern "C" int64_t tpx_stage_bind_jtable(tpx_stage* st, int64_t join_index,
+                                         const tpx_jtable* t) {
+    if (!st || !st->loaded || !t || join_index < 0) {
+        set_err("tpx_stage_bind_jtable: no loaded stage, or no table");
+        return -1;
+    }
+    if (t->dev != cur_device()) {
+        set_err("tpx_stage_bind_jtable: table lives on another device");
+        return -1;
+    }
+    hipDeviceptr_t g = nullptr;
+    size_t gbytes = 0;
+    if (hipModuleGetGlobal(&g, &gbytes, st->module, "tpx_jt") != hipSuccess) {
+        (void)hipGetLastError();
+        set_err("stage has no device join (tpx_jt not found)");
+        return -1;
+    }
+    if (((size_t)join_index + 1) * sizeof(JoinTabDesc) > gbytes) {
+        set_err("tpx_stage_bind_jtable: join_index out of range");
+        return -1;
+    }
+    xfer_h2d(sizeof(JoinTabDesc));
+    HIP_CHECK(hipMemcpy((char*)g + (size_t)join_index * sizeof(JoinTabDesc),
+                        &t->desc, sizeof(JoinTabDesc), hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -25,7 +25,7 @@ import io
 import os
 from typing import List, Optional
 
-from . import codegen, plan, rowfmt
+from . import codegen, jointab, plan, rowfmt
 from . import ttypes as T
 from . import resolve as _resolve
 from . import presolve
@@ -633,7 +633,8 @@ def run_csv(context, src, logical_ops, sink=None,
                     else (parts[0] if parts else b""))
         return data
 
-    sp = plan.build_stage(col_types, names, logical_ops)
+    sp = plan.build_stage(col_types, names, logical_ops,
+                          join_table=plan.join_table_mode(opts))
     out.output_columns = sp.output_columns  # sniffed names: cache() keeps them
     sink_kind = "csv" if (sink is not None and sink[0] == "csv") else "mem"
 
@@ -663,6 +664,17 @@ def run_csv(context, src, logical_ops, sink=None,
                                  out_cols=sp.output_columns,
                                  keep_exceptions=keep_exceptions)
     stage = glib.compile_stage(csrc, desc)
+    # device join tables: built once per (join op, device), bound before
+    # every execute below; without device memory for one, interpreter path
+    try:
+        jtabs = jointab.stage_tables(
+            glib, stage, sp, int(opts.get("tuplex.gpu.device", "0")))
+    except jointab.JoinTableAlloc as e:
+        return _run_csv_fallback(out, _load_data(), col_types,
+                                 src.null_values, logical_ops, names, sink,
+                                 str(e), delim.decode(),
+                                 out_cols=sp.output_columns,
+                                 keep_exceptions=keep_exceptions)
 
     # chunked execution at inputSplitSize boundaries (LocalBackend.cc:552-658:
     # one task per 64 MB range; here one execute per range, global row indices)
@@ -696,6 +708,7 @@ def run_csv(context, src, logical_ops, sink=None,
     out.mode = "gpu"
     out.metrics = {"t_h2d_ms": 0.0, "t_kernel_ms": 0.0, "t_d2h_ms": 0.0,
                    "bytes_in": 0, "bytes_out": 0, "chunks": len(chunks) - 1}
+    jointab.add_metrics(out.metrics, sp, jtabs)
     nch = len(chunks) - 1
     # device cache: decided here for what only the run knows; dcache["on"]
     # drops to False if a table cannot be allocated (rows then come back to
@@ -709,6 +722,8 @@ def run_csv(context, src, logical_ops, sink=None,
             where, why = "host", "not a mem-sink cache run"
         if where == "device" and (world > 1 or min(want or ndev, ndev) > 1):
             where, why = "host", "multi-device fan-out"
+        if where == "device" and jtabs:
+            where, why = "host", "stage probes a device join table"
         dcache["on"] = where == "device"
         out.cache_reason = why
         out.metrics["t_pack_ms"] = 0.0
@@ -739,6 +754,7 @@ def run_csv(context, src, logical_ops, sink=None,
                                ctypes.POINTER(ctypes.c_uint8))
         tab = ctypes.c_void_p()
         packed = False
+        jointab.bind_tables(stage_h, jtabs)
         if dcache["on"]:
             if resident_dev:
                 rc = glib.lib.tpx_stage_cache_csv_dev(

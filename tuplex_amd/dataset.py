@@ -87,7 +87,11 @@ class DataSet:
             rrows = list(dsRight._source.data)  # no pipeline: direct
         else:
             rrows = dsRight.collect()
-        rrows = [(v if isinstance(v, tuple) else (v,)) for v in rrows]
+        # BuildRows: a list that keeps the device join tables built from it
+        # (tuplex.gpu.joinTable) for the life of every DataSet derived here
+        from .jointab import BuildRows
+        rrows = BuildRows((v if isinstance(v, tuple) else (v,))
+                          for v in rrows)
         return self._chain(("join", rrows, list(rcols), leftKeyColumn,
                             rightKeyColumn, how, lp, ls, rp, rs))
 

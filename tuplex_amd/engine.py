@@ -12,7 +12,7 @@ import os
 import time
 from typing import Any, List, Optional
 
-from . import codegen, plan, rowfmt, resolve
+from . import codegen, jointab, plan, rowfmt, resolve
 from . import ttypes as T
 from . import ec as EC
 
@@ -131,6 +131,23 @@ class GpuLib:
                                            ctypes.c_int64]
         lib.tpx_table_free.restype = None
         lib.tpx_table_free.argtypes = [ctypes.c_void_p]
+        # device join tables (tpx_jtable)
+        lib.tpx_jtable_build.restype = ctypes.c_int64
+        lib.tpx_jtable_build.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_int64,
+            ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
+        lib.tpx_stage_bind_jtable.restype = ctypes.c_int64
+        lib.tpx_stage_bind_jtable.argtypes = [ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_void_p]
+        lib.tpx_jtable_rows.restype = ctypes.c_int64
+        lib.tpx_jtable_rows.argtypes = [ctypes.c_void_p]
+        lib.tpx_jtable_bytes.restype = ctypes.c_int64
+        lib.tpx_jtable_bytes.argtypes = [ctypes.c_void_p]
+        lib.tpx_jtable_build_ms.restype = ctypes.c_double
+        lib.tpx_jtable_build_ms.argtypes = [ctypes.c_void_p]
+        lib.tpx_jtable_free.restype = None
+        lib.tpx_jtable_free.argtypes = [ctypes.c_void_p]
         lib.tpx_xfer_stats.restype = ctypes.c_int64
         lib.tpx_xfer_stats.argtypes = [ctypes.POINTER(ctypes.c_int64),
                                        ctypes.POINTER(ctypes.c_int64)]
@@ -195,6 +212,7 @@ def execute_stage_mem(sp: plan.StageProgram, norm_rows: List[tuple],
 
     src, desc = codegen.generate_stage(sp, source="mem", sink="mem")
     stage = glib.compile_stage(src, desc)
+    jtabs = jointab.stage_tables(glib, stage, sp, device)  # JoinTableAlloc
 
     # split the serialized rows at partition_size boundaries (row-aligned)
     cbuf = (ctypes.c_uint8 * len(buf)).from_buffer_copy(buf)
@@ -223,6 +241,7 @@ def execute_stage_mem(sp: plan.StageProgram, norm_rows: List[tuple],
             size=offs[re_] - bs, num_rows=n_rows,
             row_offsets=ctypes.cast(rel, ctypes.POINTER(ctypes.c_int64)))
     res = TpxResult()
+    jointab.bind_tables(stage, jtabs)
     rc = glib.lib.tpx_stage_execute(stage, parts, max(len(parts_meta), 1),
                                     ctypes.byref(res))
     if rc != 0:
@@ -251,6 +270,7 @@ def execute_stage_mem(sp: plan.StageProgram, norm_rows: List[tuple],
             "t_d2h_ms": res.t_d2h_ms,
             "bytes_in": res.bytes_in, "bytes_out": res.bytes_out,
         }
+        jointab.add_metrics(out.metrics, sp, jtabs)
         return out
     finally:
         glib.lib.tpx_result_free(ctypes.byref(res))
@@ -269,14 +289,21 @@ def execute_stage_col(sp: plan.StageProgram, dev_slots, n_rows: int,
     glib.lib.tpx_set_device(device)
     src, desc = codegen.generate_stage(sp, source="col", sink="mem")
     stage = glib.compile_stage(src, desc)
+    jtabs = jointab.stage_tables(glib, stage, sp, device)  # JoinTableAlloc
     arr = (ctypes.c_void_p * len(dev_slots))(
         *[ctypes.c_void_p(p or 0) for p in dev_slots])
-    return _run_col(glib, stage, sp, arr, len(dev_slots), n_rows, in_bytes)
+    er = _run_col(glib, stage, sp, arr, len(dev_slots), n_rows, in_bytes,
+                  jtabs)
+    jointab.add_metrics(er.metrics, sp, jtabs)
+    return er
 
 
-def _run_col(glib, stage, sp, arr, n_slots, n_rows, in_bytes) -> ExecResult:
-    """One tpx_stage_execute_col call over a device slot table, decoded."""
+def _run_col(glib, stage, sp, arr, n_slots, n_rows, in_bytes,
+             jtabs=()) -> ExecResult:
+    """One tpx_stage_execute_col call over a device slot table, decoded.
+    jtabs: the stage's device join tables, bound right before the run."""
     res = TpxResult()
+    jointab.bind_tables(stage, jtabs)
     rc = glib.lib.tpx_stage_execute_col(stage, arr, n_slots, n_rows,
                                         in_bytes, 0, 0, ctypes.byref(res))
     if rc != 0:
@@ -475,14 +502,22 @@ def run_collect(data: List[Any], logical_ops: List[tuple],
             fallback.append((i, v))
 
     input_types = list(T.tuple_params(row_maj))
-    sp = plan.build_stage(input_types, columns, logical_ops)
+    sp = plan.build_stage(input_types, columns, logical_ops,
+                          join_table=plan.join_table_mode(options))
 
     # GPU-reducible aggregate: the stage returns partials; replayed rows are
     # folded on top with the user's agg fn (LocalBackend.cc:1180-1207 combine;
     # by-key: createFinalHashmap LocalBackend.cc:2219)
-    if (sp.compilable and norm_rows and sp.agg_expr is not None):
-        er = execute_stage_mem(sp, norm_rows,
-                               partition_size=options.partition_size)
+    er = None
+    if sp.compilable and norm_rows:
+        try:
+            er = execute_stage_mem(sp, norm_rows,
+                                   partition_size=options.partition_size)
+        except jointab.JoinTableAlloc as e:
+            # no device memory for the join table: interpreter path
+            sp.compilable = False
+            sp.why_not_compilable = str(e)
+    if er is not None and sp.agg_expr is not None:
         out.mode = "gpu"
         out.metrics = er.metrics
         replay = [(norm_idx[r], data[norm_idx[r]]) for (r, _, _) in er.exceptions]
@@ -529,9 +564,7 @@ def run_collect(data: List[Any], logical_ops: List[tuple],
         return out
 
     results = {}  # original index -> row value
-    if sp.compilable and norm_rows:
-        er = execute_stage_mem(sp, norm_rows,
-                               partition_size=options.partition_size)
+    if er is not None:
         out.mode = "gpu"
         out.metrics = er.metrics
         # outputs carry their exact local row index (out_row_indices) -> map back
@@ -679,7 +712,9 @@ def run_dcached(context, src, post_ops, keep_exceptions=False):
     sp = None
     if ops2 and not keep_exceptions and \
             plan.find_dup_join_split(ops2) is None:
-        sp = plan.build_stage(types, names, ops2)
+        sp = plan.build_stage(types, names, ops2,
+                              join_table=plan.join_table_mode(
+                                  context.options_obj))
         if sp.compilable:
             try:
                 csrc, desc = codegen.generate_stage(sp, source="col",
@@ -695,6 +730,12 @@ def run_dcached(context, src, post_ops, keep_exceptions=False):
     glib = GpuLib.get()
     glib.lib.tpx_set_device(src.device)
     stage = glib.compile_stage(csrc, desc)
+    try:
+        jtabs = jointab.stage_tables(glib, stage, sp, src.device)
+    except jointab.JoinTableAlloc:
+        # no device memory for the join table: the host-cache path replays
+        return run_cached(context, src.host_source(), post_ops,
+                          keep_exceptions=keep_exceptions)
     scalar_input = len(types) == 1
     out = CollectOutcome()
     out.mode = "gpu"
@@ -719,7 +760,8 @@ def run_dcached(context, src, post_ops, keep_exceptions=False):
         if not tab.rows:
             continue
         arr, _nb = tab.slots()
-        er = _run_col(glib, stage, sp, arr, len(arr), tab.rows, tab.bytes)
+        er = _run_col(glib, stage, sp, arr, len(arr), tab.rows, tab.bytes,
+                      jtabs)
         for k, v in er.metrics.items():
             out.metrics[k] += v
         keys = tab.keys
@@ -747,6 +789,7 @@ def run_dcached(context, src, post_ops, keep_exceptions=False):
     for key, payload in src.pending:
         take(key, src.replayer(payload, full_ops))
 
+    jointab.add_metrics(out.metrics, sp, jtabs)
     agg_cols = sp.output_columns
     if sp.agg_expr is not None:
         host_rows = [v for _, v in sorted(host_pairs, key=lambda t: t[0])]

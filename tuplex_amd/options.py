@@ -58,6 +58,10 @@ DEFAULTS = {
     "tuplex.gpu.devices": "1",            # in-process device fan-out (N>1 opt-in; 0 = all visible)
     "tuplex.gpu.resolveProcesses": "0",   # parallel host resolver width (0 = auto, 1 = inline)
     "tuplex.gpu.deviceCache": "true",     # cache() keeps columnar partitions in HBM where it can
+    # where a unique-key join's build side lives: auto (embedded in the
+    # generated source up to 65,536 rows / 4 MiB of strings, else a device
+    # join table in HBM) | embedded | device
+    "tuplex.gpu.joinTable": "auto",
 }
 
 

@@ -15,7 +15,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import plan, resolve
+from . import jointab, plan, resolve
 from . import ttypes as T
 from .engine import CollectOutcome, GpuLib, execute_stage_col, _agg_row, \
     _unwrap_row
@@ -79,7 +79,8 @@ def run_orc(ctx, src, logical_ops, sink=None, keep_exceptions=False):
     for k, b in enumerate(bases):
         col_types.append(("opt", b) if tab.column(k).null_count > 0 else b)
 
-    sp = plan.build_stage(col_types, names, logical_ops)
+    sp = plan.build_stage(col_types, names, logical_ops,
+                          join_table=plan.join_table_mode(ctx.options_obj))
     if not sp.compilable:
         return _fallback_all(out, tab, names, logical_ops,
                              sp.why_not_compilable,
@@ -144,6 +145,10 @@ def run_orc(ctx, src, logical_ops, sink=None, keep_exceptions=False):
                              .tobytes()), 0, null_ptr]
 
         er = execute_stage_col(sp, slots, n_rows, total_bytes)
+    except jointab.JoinTableAlloc as e:
+        # no device memory for the join table: interpreter path
+        return _fallback_all(out, tab, names, logical_ops, str(e),
+                             out_cols=sp.output_columns)
     finally:
         for p in dev_ptrs:
             glib.lib.tpx_dev_free(p)

@@ -102,13 +102,75 @@ class StageProgram:
         return hashlib.sha256(json.dumps(desc, sort_keys=True).encode()).hexdigest()[:16]
 
 
-def build_stage(input_types, input_columns, logical_ops) -> StageProgram:
+JOIN_TABLE_MODES = ("auto", "embedded", "device")
+JOIN_DEVICE_MAX_ROWS = 1 << 30
+JOIN_DEVICE_MAX_COLS = 64     # TPX_JOIN_MAX_COLS (csrc/tpx_join.hip.h)
+
+
+def join_table_mode(options) -> str:
+    """The join_table keyword of build_stage for a Context's options
+    (tuplex.gpu.joinTable). The in-process multi-device thread pool
+    (tuplex.gpu.devices > 1) shares one stage module's table binding between
+    its workers, so it keeps the embedded table; rank-sharded runs are one
+    device per process and take the option as it stands."""
+    mode = str(options.get("tuplex.gpu.joinTable", "auto") or "auto").lower()
+    if mode not in JOIN_TABLE_MODES:
+        raise ValueError("tuplex.gpu.joinTable must be one of %s, not %r"
+                         % ("/".join(JOIN_TABLE_MODES), mode))
+    if int(options.get("tuplex.gpu.devices", "1") or "0") != 1:
+        return "embedded"
+    return mode
+
+
+_JOIN_KIND_OF = {int: "i64", float: "f64", bool: "bool", str: "str"}
+
+
+def _join_device_schema(rrows, rcols, rki, rtypes):
+    """Schema of a build side the device join table can hold, or None:
+    {"key_str", "cols": [(j, kind, has_null)] for every right column except
+    the key}. Every column must hold values of ONE python type among int /
+    float / bool / str (plus None outside the key), agreeing with the sampled
+    column type the plan threads downstream."""
+    if len(rrows) > JOIN_DEVICE_MAX_ROWS or len(rcols) > JOIN_DEVICE_MAX_COLS:
+        return None
+    cols = []
+    key_str = False
+    for j in range(len(rcols)):
+        kinds = set(map(type, (r[j] for r in rrows)))
+        has_null = type(None) in kinds
+        kinds.discard(type(None))
+        if len(kinds) > 1 or (j == rki and has_null):
+            return None
+        if kinds:
+            kind = _JOIN_KIND_OF.get(next(iter(kinds)))
+            if kind is None or (rrows and T.deopt(rtypes[j]) != kind):
+                return None
+        else:
+            kind = "i64"   # empty or all-None column, like the embedded table
+        if j == rki:
+            if kind not in ("i64", "str"):
+                return None
+            key_str = kind == "str"
+        else:
+            cols.append((j, kind, has_null))
+    return {"key_str": key_str, "cols": cols}
+
+
+def build_stage(input_types, input_columns, logical_ops,
+                join_table="auto") -> StageProgram:
     """logical_ops: list of tuples as produced by DataSet:
     ("map", fn) ("filter", fn) ("withColumn", col, fn) ("mapColumn", col, fn)
     ("selectColumns", [cols]) ("renameColumn", old, new)
     ("resolve", exc_class, fn) ("ignore", exc_class)
     ("aggregate", combine_fn, agg_fn, initial)
+
+    join_table: where the build side of a unique-key join lives — "embedded"
+    (arrays in the generated source, at most 65,536 rows / 4 MiB of strings),
+    "device" (a device join table in HBM wherever the build side is
+    eligible), or "auto" (embedded where it fits, else device).
     """
+    if join_table not in JOIN_TABLE_MODES:
+        raise ValueError("join_table must be one of %r" % (JOIN_TABLE_MODES,))
     sp = StageProgram(input_types, input_columns)
     cur_types = list(input_types)
     cur_cols = list(input_columns) if input_columns else None
@@ -257,19 +319,34 @@ def build_stage(input_types, input_columns, logical_ops) -> StageProgram:
                                           optional_threshold=1.0)
                 rtypes.append(T.tuple_params(T.row_type_of(t))[0])
             lkt = T.deopt(cur_types[lki])
+            types_ok = True
             if T.deopt(rtypes[rki]) != lkt or lkt not in (T.I64, T.STR):
+                types_ok = False
                 _fallback(sp, "join key type %r/%r (i64/str only on GPU)"
                           % (cur_types[lki], rtypes[rki]))
             if any(T.deopt(t) not in (T.I64, T.F64, T.BOOL, T.STR)
                    for t in rtypes):
+                types_ok = False
                 _fallback(sp, "join: unsupported right column type")
-            if len(rrows) > 65536 or sum(
+            # device join table (tpx_jtable): "device" wherever the build
+            # side is eligible, "auto" only where the embedded table refuses
+            dev_schema = None
+            if join_table == "embedded" or op._join_dup:
+                types_ok = False
+            if types_ok and (join_table == "device" or len(rrows) > 65536):
+                dev_schema = _join_device_schema(rrows, rcols, rki, rtypes)
+            if dev_schema is None and (len(rrows) > 65536 or sum(
                     len(str(r[j]).encode()) for r in rrows
                     for j in range(len(rcols))
-                    if isinstance(r[j], str)) > (4 << 20):
-                _fallback(sp, "join build side too large for the embedded "
-                          "table this round")
+                    if isinstance(r[j], str)) > (4 << 20)):
+                if types_ok:
+                    # too many string bytes for the source, few enough rows
+                    dev_schema = _join_device_schema(rrows, rcols, rki, rtypes)
+                if dev_schema is None:
+                    _fallback(sp, "join build side too large for the embedded "
+                              "table this round")
             op.join = (rrows, rcols, lki, rki, how)
+            op.join_dev = dev_schema
             out_r = []
             for j, t in enumerate(rtypes):
                 if j == rki:
@@ -298,6 +375,11 @@ def build_stage(input_types, input_columns, logical_ops) -> StageProgram:
                           "mid-pipeline: interpreter path this round")
             else:
                 op.join_dup = True
+    # device join tables, in op order: entry i of the stage's tpx_jt[]
+    sp.device_joins = [op for op in sp.ops if op.kind == "join"
+                       and getattr(op, "join_dev", None) is not None]
+    for i2, op in enumerate(sp.device_joins):
+        op.join_dev["index"] = i2
     sp.used_source_cols = _used_source_columns(sp) if sp.compilable else None
     return sp
 
